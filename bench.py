@@ -7,7 +7,9 @@ already resident in HBM.  Step k uses case numbers k*n+1 .. (k+1)*n of the same 
 no step repeats another's work.  Multi-GPU: rank r holds the (RCCL-broadcast) arena and runs its
 own contiguous range of case numbers — weak scaling, no data-path collective.
 
-Prints ONE JSON line on rank 0 (see the driver contract in the task statement).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and prints the line; --full adds the
+legs that are not part of the headline (CPU oracle + parity check, PCIe, work budget, strong scaling), --dump-outputs DIR
+writes what the last timed step computed.
 """
 import argparse
 import json
@@ -130,6 +132,38 @@ def kernel_source_sha1():
     return h.hexdigest()
 
 
+DUMP_SAMPLE = 1024     # --dump-outputs: cases whose output bytes are written (a fixed, seeded sample of the pass)
+DUMP_HEAD = 4096       # ... and how many leading bytes of each
+
+
+def dump_outputs(path, e):
+    """--dump-outputs: what a caller of eh_fuzz_batch receives from the pass `e` last ran, as float64 / float32 .npy files
+    (about 18 MB for 65536 cases; a whole pass's outputs are tens of GB):
+      status.npy         float64[n]   every case's status (0 ok, 1 crashed, 2 overflow, 3 unsupported, 4 arena full, 5 budget)
+      lengths.npy        float64[n]   every case's output length in bytes
+      sample_index.npy   float64[S]   the sampled cases (indices into the pass; PCG64(0xD0) over n, sorted)
+      sample_head.npy    float32[S, DUMP_HEAD]  the first DUMP_HEAD bytes of each sampled output, -1 past its end
+      sample_sha1.npy    float32[S, 20]         the SHA-1 of each sampled output in full, byte by byte"""
+    import hashlib
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    st, ln = e.status(), e.lens()
+    n = len(st)
+    idx = np.sort(np.random.Generator(np.random.PCG64(0xD0)).choice(n, size=min(DUMP_SAMPLE, n), replace=False))
+    head = np.full((len(idx), DUMP_HEAD), -1.0, dtype=np.float32)
+    sha = np.zeros((len(idx), 20), dtype=np.float32)
+    for j, i in enumerate(idx):
+        b = e.fetch(int(i), int(ln[i]))
+        h = np.frombuffer(b[:DUMP_HEAD], dtype=np.uint8)
+        head[j, :len(h)] = h
+        sha[j] = np.frombuffer(hashlib.sha1(b).digest(), dtype=np.uint8)
+    arrays = {"status": st.astype(np.float64), "lengths": ln.astype(np.float64), "sample_index": idx.astype(np.float64),
+              "sample_head": head, "sample_sha1": sha}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(arrays)
+
+
 def log(msg):
     sys.stderr.write("[bench %.1f] %s\n" % (time.time() % 100000, msg))
     sys.stderr.flush()
@@ -152,7 +186,7 @@ def main():
     ap.add_argument("--config", type=int, default=3, choices=[3, 5], help="3 = BASELINE configs[2] (the default, what the driver times); 5 = the shape of "
                     "configs[4]: 131072 x world seeds of 64 KiB from the counter-hash corpus, generator jump (cross-seed splices), mutators "
                     "ft,fn,fo,num,len, pattern sz, strong scaling (every rank holds the whole arena and runs its share of the cases); other flags override")
-    ap.add_argument("--cpu-sample", type=int, default=2048, help="cases timed on the CPU oracle: the first N of the run (0 = skip)")
+    ap.add_argument("--cpu-sample", type=int, default=2048, help="--full: cases timed on the CPU oracle: the first N of the run (0 = skip)")
     ap.add_argument("--cpu-case-seconds", type=float, default=10.0, help="per-case wall-clock watchdog of the CPU oracle leg "
                     "(the reference's maxrunningtime; its CLI default is 30 s)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the CPU oracle leg (0 = all host cores, at most 64)")
@@ -167,11 +201,11 @@ def main():
                     "outgrows it borrows larger areas from the pool")
     ap.add_argument("--big-mib", type=int, default=1024, help="largest work area (MiB), eh_options.big_case_bytes: a case that outgrows its area "
                     "borrows areas of 2x, 4x, ... from the pool, up to this size")
-    ap.add_argument("--budget-mib", type=int, default=64, help="after the headline run (no budget), repeat 3 steps with this per-case work "
+    ap.add_argument("--budget-mib", type=int, default=64, help="--full: after the headline run (no budget), repeat 3 steps with this per-case work "
                     "budget (eh_options.max_case_work) and report them under 'with_work_budget'; 0 = skip")
     ap.add_argument("--work-mib", type=int, default=0, help="optional per-case work budget (MiB), eh_options.max_case_work; "
                     "0 = off (default): every case runs to completion like under the reference's 30 s CLI watchdog")
-    ap.add_argument("--pcie", type=int, default=1, help="1: after the timed steps, one extra pass whose outputs are downloaded to pinned host memory "
+    ap.add_argument("--pcie", type=int, default=1, help="1 (with --full): after the timed steps, one extra pass whose outputs are downloaded to pinned host memory "
                     "(reported as 'pcie'); 0: skip")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"], help="weak (default): every rank runs its own 64 K case numbers per step; "
                     "strong: a step is ONE run of --cases cases split over the ranks by shard.case_range (erlamsa_main.erl:95-108)")
@@ -185,12 +219,17 @@ def main():
     ap.add_argument("--setup-seconds", type=int, default=150, help="single-GPU runs execute in a child process; a child whose set-up passes (the first "
                     "dispatch on every HIP stream) have not finished after this many seconds is killed and the run repeated with "
                     "--inflight 3, then 1 (0 = no supervision)")
-    ap.add_argument("--strong-leg", type=int, default=1, help="N > 1 with weak scaling: after the timed steps, a few steps of STRONG scaling (one run of --cases cases "
+    ap.add_argument("--strong-leg", type=int, default=1, help="N > 1 with weak scaling and --full: after the timed steps, a few steps of STRONG scaling (one run of --cases cases "
                     "split over the ranks by shard.case_range, what north_star's corpus sharding is) reported under 'strong_scaling_leg'; 0 = skip")
     ap.add_argument("--case-stats", type=int, default=1, help="1: collect per-case wave cycles and output lengths of the timed steps (one small D2H copy per "
                     "collected pass, outside no kernel's way) and report them under 'case_stats': how the bytes and the cycles are distributed over the cases")
-    ap.add_argument("--profiled", type=int, default=0, help="1: the run is under rocprofv3 - no child process (--setup-seconds 0) and the process ends by "
-                    "returning from main() instead of os._exit, so that the profiler's tool gets to write its output")
+    ap.add_argument("--profiled", type=int, default=0, help="1: the run is under rocprofv3 - no child process (--setup-seconds 0), and a leg that outlives "
+                    "--extras-seconds does not end the process early, so that the profiler's tool gets to write its output")
+    ap.add_argument("--full", action="store_true", help="after the headline result, also run the legs that are not part of it: the CPU oracle leg "
+                    "with its parity check (--cpu-sample), the PCIe leg (--pcie), the work-budget leg (--budget-mib) and, for N > 1 with weak "
+                    "scaling, the strong-scaling leg (--strong-leg).  Off (default): set-up, warm-up, the timed steps and the result line only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last timed step of rank 0 "
+                    "computed as DIR/<name>.npy (see dump_outputs)")
     pre, _ = ap.parse_known_args()
     if pre.config == 5:
         w5 = int(os.environ.get("WORLD_SIZE", "1"))
@@ -199,6 +238,8 @@ def main():
     args = ap.parse_args()
     if args.profiled:
         args.setup_seconds = 0
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step")
 
     # ---- supervision (single GPU only): the run proper happens in a child process, and the driver must get its JSON line.
     # A child that dies (round 3's driver run: "Memory access fault by GPU node-2" 3.6 s in, once, never reproduced) or that never
@@ -429,8 +470,11 @@ def main():
     names = [m for m, _, _ in ea.mutator_table()]
 
     cyc_pass, len_hist, occ_pass = [], [], []
+    last_pass = {"step": -1, "engine": None}                  # the context that ran the last timed step (--dump-outputs)
 
     def on_result(k, e):                                      # which capacity check gave up, for the cases that end as EH_CASE_OVERFLOW
+        if k > last_pass["step"]:
+            last_pass["step"], last_pass["engine"] = k, e
         st = e.status()
         occ_pass.append(e.occupancy())                          # (page-locked memory the kernel wrote: no copy call)
         if args.case_stats:
@@ -458,11 +502,14 @@ def main():
     dt = time.perf_counter() - t0
     log("timed steps done: %.3f s per step" % (dt / max(args.steps, 1)))
     out_bytes, kern_ms, status_counts = timed["out_bytes"], timed["kernel_ms"], timed["status_counts"]
+    if args.dump_outputs and rank == 0:                       # before any leg runs another pass on that context
+        dumped = dump_outputs(args.dump_outputs, last_pass["engine"])
+        log("outputs of step %d written to %s: %s" % (last_pass["step"], args.dump_outputs, ", ".join(dumped)))
 
     my_cases = (shard.case_range(n, rank, world)[1] if strong else n) * args.steps
     dt_all, out_all, cases_all = shard.reduce_over_ranks(dt, out_bytes, my_cases, dist, dev)
     strong_leg = None
-    if world > 1 and not strong and args.strong_leg and args.steps > 0:
+    if args.full and world > 1 and not strong and args.strong_leg and args.steps > 0:
         # the same corpus, strong scaling: ONE run of n cases per step, rank r takes case_range(n, r, world) of it (erlamsa_main.erl:95-108).
         # A rank's pass is 1 / world of a weak one, so world x as many passes go through a GPU per second and the leg needs world x as
         # many steps as the weak run before ramp and drain of the pipeline stop showing: 4 x contexts x world steps (at most 200),
@@ -596,8 +643,8 @@ def main():
         if int(status_counts[4]) > 0:                             # EH_CASE_ARENA_FULL inside the timed steps: those cases' outputs are missing from `value`
             res["warning"] = "%d cases of the timed steps did not fit their pass's output arena (%d GiB): raise --out-gib; value counts the bytes that were produced" % (int(status_counts[4]), args.out_gib)
             log(res["warning"])
-        # ---- legs that are not the headline: they run AFTER the result exists, under a watchdog that prints the line without them
-        # if one of them does not come back (a hung leg must not cost the measured result)
+        # ---- legs that are not the headline (--full only): they run AFTER the result exists, under a watchdog that prints the line
+        # without them if one of them does not come back (a hung leg must not cost the measured result)
         def leg_pcie():
             # PCIe-inclusive leg: one more pass whose outputs are also brought to host memory, case-ordered, through the
             # boundary call a host-side consumer uses (eh_result_download into pinned memory)
@@ -681,7 +728,7 @@ def main():
             if not args.profiled:
                 os._exit(0)
 
-        if world == 1:
+        if world == 1 and args.full:
             threading.Thread(target=watchdog, daemon=True).start()
             # the CPU oracle leg first: it is also the parity check of this very run
             reduced = None
@@ -728,8 +775,8 @@ def main():
                 res["with_work_budget"] = leg_budget()
         emit()
         sys.stdout.flush()
-        if world == 1 and not args.profiled:
-            os._exit(0)                                              # (tearing six contexts down takes seconds the driver's clock would count)
+        # (the process ends by returning from main(): the contexts are torn down and the exit handlers of the process run, so that
+        # every tool that reports at exit - a profiler, a tracer of loaded code - gets to write its output)
     if dist is not None:
         dist.destroy_process_group()
 

@@ -26,7 +26,7 @@ def _run(extra):
 
 
 def test_bench_script_runs_end_to_end_on_the_emulator():
-    d = _run(["--cases", "16", "--size", "256", "--mutations", "bd,bf,bi,sr,num,lr,ab", "--budget-mib", "1", "--pcie", "1"])
+    d = _run(["--full", "--cases", "16", "--size", "256", "--mutations", "bd,bf,bi,sr,num,lr,ab", "--budget-mib", "1", "--pcie", "1"])
     assert d["metric"] == "mutated_MB_per_s" and d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["scaling"] == "weak"
     assert d["value"] > 0 and d["ms_per_step"] > 0 and d["config"]["cases_per_step_per_gpu"] == 16
     # --cpu-sample 8 = rows 0..3 of THREE passes of the run (the first, one in the middle, the last: bench.parity_windows)
@@ -41,9 +41,40 @@ def test_bench_script_runs_end_to_end_on_the_emulator():
 
 
 def test_bench_config_5_shape_runs_on_the_emulator():
-    d = _run(["--config", "5", "--cases", "12", "--size", "4096", "--budget-mib", "0", "--pcie", "0", "--steps", "1", "--warmup", "0", "--inflight", "1", "--cpu-sample", "6"])
+    d = _run(["--full", "--config", "5", "--cases", "12", "--size", "4096", "--budget-mib", "0", "--pcie", "0", "--steps", "1", "--warmup", "0", "--inflight", "1", "--cpu-sample", "6"])
     assert "configs[4]" in d["config"]["workload"] and "generator jump" in d["config"]["workload"] and d["scaling"] == "strong"
     assert d["case_status"]["ok"] == 12 and d["parity_checked"] == 6        # the oracle's Paths are the whole counter-hash arena
+
+
+def test_plain_run_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """Without --full the line is the headline alone (no oracle, PCIe or work-budget leg); --steps sets the timed steps; --dump-outputs
+    writes the statuses, lengths and sampled outputs of the LAST timed step, the same from run to run, and they are the oracle's."""
+    import hashlib
+    import numpy as np
+    import pyoracle as po
+    from erlamsa_amd import synth
+    muts = "bd,bf,bi,sr,num,lr,ab"
+    args = ["--cases", "16", "--size", "256", "--mutations", muts, "--steps", "3"]
+    runs = []
+    for k in range(2):
+        d = _run(args + ["--dump-outputs", str(tmp_path / str(k))])
+        assert d["metric"] == "mutated_MB_per_s" and d["unit"] == "MB/s" and d["higher_is_better"] is True and "dtype" in d
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["case_status"]["ok"] == 48
+        assert not {"cpu_baseline", "parity", "parity_checked", "pcie", "with_work_budget"} & set(d)
+        runs.append({f[:-4]: np.load(tmp_path / str(k) / f) for f in os.listdir(tmp_path / str(k))})
+    a, b = runs
+    assert set(a) == {"status", "lengths", "sample_index", "sample_head", "sample_sha1"}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    # warm-up step 0, timed steps 1..3: the last one ran case numbers 3 * 16 + 1 .. 4 * 16 (shard.weak_first_case)
+    data, off = synth.as_arena(synth.mixed(16, 256))
+    outs, st, _, _ = po.fuzz_batch(data, off, seed=(1, 2, 3), mutations=muts, patterns="od,nd,bu", first_case=3 * 16 + 1, max_case_bytes=32 << 20)
+    assert a["status"].tolist() == [float(s) for s in st] and a["lengths"].tolist() == [float(len(o)) for o in outs]
+    assert a["sample_index"].tolist() == list(range(16))
+    for j, o in enumerate(outs):
+        assert a["sample_sha1"][j].astype(np.uint8).tobytes() == hashlib.sha1(o).digest()
+        h = a["sample_head"][j]
+        assert bytes(h[h >= 0].astype(np.uint8)) == o[:h.size] and (h[:len(o)] >= 0).all()
 
 
 @pytest.mark.parametrize("scaling", ["weak", "strong", "weak-without-rccl"])
@@ -64,7 +95,7 @@ def test_bench_script_two_ranks_over_gloo_on_the_emulator(scaling):
         scaling = "weak"
     port = 29700 + (os.getpid() % 200) + (2 if no_rccl else 0 if scaling == "weak" else 1)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--scaling", scaling, "--cases", "16", "--size", "256", "--mutations", "bd,bf,bi,sr,num,lr,ab"] + SMALL
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--scaling", scaling, "--cases", "16", "--size", "256", "--mutations", "bd,bf,bi,sr,num,lr,ab"] + SMALL
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, r.stdout[-1500:] + r.stderr[-3000:]

@@ -23,12 +23,12 @@ def _engine_env():
 
 
 def test_bench_script_on_the_device():
-    """The driver's command with fewer steps: `python bench.py --gpus 1 --steps 2 --warmup 1` as a subprocess on the real device
-    (round 3's driver run of it died before its set-up passes and printed nothing).  The line must be BASELINE configs[2] and
-    carry roofline, cpu_baseline and a parity count."""
+    """The driver's command with fewer steps and the legs of --full: `python bench.py --full --gpus 1 --steps 2 --warmup 1` as a
+    subprocess on the real device (round 3's driver run of it died before its set-up passes and printed nothing).  The line must be
+    BASELINE configs[2] and carry roofline, cpu_baseline and a parity count."""
     if util.priming():
         pytest.skip("no oracle cache involved")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--budget-mib", "0"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "2", "--warmup", "1", "--budget-mib", "0"],
                        env=_engine_env(), capture_output=True, text=True, timeout=900)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, r.stdout[-1500:] + r.stderr[-3000:]
