@@ -37,6 +37,34 @@ struct IsOpener { EH_DEV bool operator()(uint32_t b, uint32_t) const { return de
 // open position (pre-order), or -1 on allocation failure.  The matcher only looks at delimiter
 // bytes (mask events); its stack lives in lane registers (entry d in lane d - base), spilling 32
 // entries at a time to the work area for nesting deeper than 64.
+//
+// Lane batches.  What a run of consecutive events does depends on the stack below it in two places only: a non-quote closer met
+// with the run's own stack empty pops the outer top or is ignored (an ESCAPING closer: the run's own state is the same either way),
+// and a quote met with the run's own stack empty closes the outer top or is pushed (a STOP: the states differ).  With a non-empty
+// local stack the true top is the local top and every decision is final.  So a batch is 64 runs of TL_S events, lane k runs the
+// machine over run k from an empty local stack (in LDS) and keeps what it did per event; the wave then walks the lanes in order
+// against the real stack: escaping closers are resolved against the real top, the run's unclosed openers are pushed, and nodes
+// opened at local depth 0 get the real top of that moment as parent.  A run that stopped is valid up to the stop; the walk decides
+// that quote and the rest of that run one event after the other against the real stack, and goes on with the next lane: the runs
+// behind are summaries of their own events and stay valid whatever came before them.  Lane 0 starts where the real stack is, so it
+// knows the real top (until one of its events pops it) and decides its first quotes itself.
+#ifndef EH_TREE_S
+#define EH_TREE_S 32
+#endif
+constexpr uint32_t TL_S = EH_TREE_S;                   // events per run (per-run event sets are 32-bit masks)
+constexpr uint32_t TL_SP = TL_S + 4;                   // bytes per lane in the per-event byte arrays (word stride 9: no bank conflicts)
+constexpr uint32_t TL_COD = 0;                         // g_fuse_lds words: delimiter code of event j of lane k at byte k * TL_SP + j
+constexpr uint32_t TL_LNK = TL_COD + 16 * TL_SP;       // link: closing event -> its opener's j; pushed opener -> local parent's j (255: none)
+constexpr uint32_t TL_STK = TL_LNK + 16 * TL_SP;       // local stacks, uint16 [TL_S][64]: j << 4 | closer code
+constexpr uint32_t TL_TOP = TL_STK + 32 * TL_S;        // uint32 [64][TL_S]: real top slot after the lane's e-th escaping closer
+constexpr uint32_t TL_ESC = TL_TOP + 64 * TL_S;        // bytes [64][TL_SP]: the run's escaping closers in order (their j)
+constexpr uint32_t TL_TAIL = 4 * TL_S;                 // fewer events than this are left to the sequential loop
+constexpr uint32_t TL_SEQ_MIN = 1024, TL_SEQ_MAX = 65536;  // a batch whose walk decided more than half of the events one by one sends the next
+                                                           // stretch of this many events to the sequential loop: doubles on failure, halves on success
+static_assert(TL_S >= 8 && TL_S <= 32 && TL_S % 4 == 0, "tree_parse: per-run event masks are 32 bits wide");
+static_assert(TL_ESC + 16 * TL_SP <= EH_FUSE_LDS_WORDS, "g_fuse_lds too small for the lane batches of tree_parse");
+EH_DEV uint8_t* tl_bytes() { return reinterpret_cast<uint8_t*>(g_fuse_lds); }
+EH_DEV uint16_t* tl_stack() { return reinterpret_cast<uint16_t*>(g_fuse_lds + TL_STK); }
 #ifdef EH_PROF
 #define TR_PH(k) do { uint64_t now_ = __builtin_readcyclecounter(); if (EH_LANE == 0) { atomicAdd(&c.p->prof[2 * (70 + (k))], (unsigned long long)(now_ - tph)); atomicAdd(&c.p->prof[2 * (70 + (k)) + 1], 1ull); } tph = now_; } while (0)
 #define TR_ST(k, v) do { if (EH_LANE == 0) { atomicAdd(&c.p->prof[2 * (70 + (k))], (unsigned long long)(v)); atomicAdd(&c.p->prof[2 * (70 + (k)) + 1], 1ull); } } while (0)
@@ -44,16 +72,46 @@ struct IsOpener { EH_DEV bool operator()(uint32_t b, uint32_t) const { return de
 #define TR_PH(k) do { } while (0)
 #define TR_ST(k, v) do { } while (0)
 #endif
+#ifdef HIPEMU
+// the CPU emulator build counts what the lane batches did (tests/test_tree_lanes.py): events committed, batches, batches that fell short;
+// parses that ran lane batches and their events
+extern "C" { inline unsigned long long eh_emu_tree_lanes[5] = {0, 0, 0, 0, 0}; }
+#define TL_COUNT(i, v) do { if (EH_LANE == 0) eh_emu_tree_lanes[i] += (v); } while (0)
+#else
+#define TL_COUNT(i, v) do { } while (0)
+#endif
 struct IsDelim { EH_DEV bool operator()(uint32_t b, uint32_t) const { return delim_bit(b, (1u << 2) | (1u << 7) | (1u << 8) | (1u << 9) | (1u << 28) | (1u << 30), (1u << 27) | (1u << 29)); } };
+// delimiters and openers among the 16 bytes of the tile that are mine: one load, both byte classes (bit k = byte k)
+EH_DEV void delim_tile_masks(cbptr p, uint32_t n, uint32_t tile_base, uint32_t& md, uint32_t& mo, uint32_t& mq) {
+  md = 0; mo = 0; mq = 0;                                       // (mq, the quotes: EH_PROF builds only)
+  uint32_t i0 = tile_base + 16u * (uint32_t)EH_LANE;
+  if (i0 >= n) return;
+  uint32_t cnt = n - i0 < 16 ? n - i0 : 16;
+  uint8_t b[16];
+  if (cnt == 16) { uint4 v = ldg16(p + i0); __builtin_memcpy(b, &v, 16); }
+  else { for (uint32_t k = 0; k < 16; k++) b[k] = k < cnt ? p[i0 + k] : 0; }
+#pragma unroll
+  for (uint32_t k = 0; k < 16; k++) {
+    if (IsDelim()((uint32_t)b[k], 0)) md |= 1u << k;          // (a padding byte is 0: no delimiter)
+    if (IsOpener()((uint32_t)b[k], 0)) mo |= 1u << k;
+#ifdef EH_PROF
+    if (b[k] == 34 || b[k] == 39) mq |= 1u << k;
+#endif
+  }
+}
 __device__ __noinline__ int tree_parse(Ctx&, cbptr H, uint32_t L, EH_G TNode** out) {
   EH_CTX;
   const int l = EH_LANE;
 #ifdef EH_PROF
   uint64_t tph = __builtin_readcyclecounter();
 #endif
-  // 1. positions of all delimiter bytes, in order (parallel scan + compaction)
-  uint32_t nev = wave_count(H, L, IsDelim());
-  uint32_t nopen = wave_count(H, L, IsOpener());
+  // 1. positions of all delimiter bytes, in order (parallel scan + compaction); delimiters and openers are counted in one pass
+  uint32_t nev = 0, nopen = 0, nquote = 0;
+  for (uint32_t tb = 0; tb < L; tb += 1024) { uint32_t md, mo, mq; delim_tile_masks(H, L, tb, md, mo, mq); nev += __popc(md); nopen += __popc(mo); nquote += __popc(mq); }
+  nev = wave_sum(nev); nopen = wave_sum(nopen);
+#ifdef EH_PROF
+  nquote = wave_sum(nquote);
+#endif
   EH_G TNode* tab = (EH_G TNode*)ws_alloc(c, (uint64_t)(nopen + 1) * sizeof(TNode));
   wptr spill = (wptr)ws_alloc(c, (uint64_t)(nopen + 64) * 4);
   wptr evp = (wptr)ws_alloc(c, (uint64_t)(nev + 64) * 4);
@@ -62,81 +120,296 @@ __device__ __noinline__ int tree_parse(Ctx&, cbptr H, uint32_t L, EH_G TNode** o
   TR_PH(10);
   wave_collect(H, L, 0, nev, evp, IsDelim());
   TR_PH(11); TR_ST(15, nev);
-  // 2. the matcher walks the event list 64 events at a time; positions and delimiter codes sit in
-  //    registers (lane i = event i of the batch), the stack in lane registers too.  The inner loop
-  //    touches no memory: on this ISA stores count in vmcnt, so a store per event makes every
-  //    iteration wait for the previous one's write (~600 cycles).  Pushes and closes of a batch are
-  //    buffered in lane registers (k-th push / k-th close of the batch in lane k) and written with one
-  //    coalesced store / one scatter per batch.
+  // 2. the matcher.  A node's slot in the table is the rank of its opener among the opener events (monotone in the open position,
+  //    and known without running the machine); opener events that pushed nothing (a quote that closed) leave their slot unused.
+  //    No loop that decides events touches global memory: on this ISA stores count in vmcnt, so a store per event makes every
+  //    iteration wait for the previous one's write (~600 cycles).  Pushes and closes are buffered in lane registers (k-th push /
+  //    k-th close in lane k) and written 64 at a time.  The table holds EVENT NUMBERS in open / close until the compaction at the
+  //    end turns them into positions: the loops that write records then only store, they never wait for a load.
   for (uint32_t i = (uint32_t)l; i < nopen + 1; i += 64) tab[i].close = 0xFFFFFFFFu;
   wave_sync();
   uint32_t stk = 0;                      // my stack entry: slot << 8 | expected closer code
   uint32_t sp = 0, sbase = 0;            // depth, depth held by lane 0
-  uint32_t nslots = 0, top = 0;          // top = copy of the top entry
-  for (uint32_t eb = 0; eb < nev; eb += 64) {
-    uint32_t mypos = eb + (uint32_t)l < nev ? evp[eb + l] : 0;
-    uint32_t mycode = eb + (uint32_t)l < nev ? DelimCls()((uint32_t)H[mypos]) : 0;
-    // bit 8: opener; bits 16..23: the closer code an opener waits for
-    mycode |= delim_is_opener(mycode) ? (0x100u | (delim_close_code(mycode) << 16)) : 0u;
-    uint32_t cnt = nev - eb < 64 ? nev - eb : 64;
-    uint32_t first = nslots, npush = 0, nclose = 0;
-    uint32_t po = 0, pp = 0, cs = 0, cp = 0;
-    for (uint32_t e = 0; e < cnt; e++) {
-      uint32_t code = (uint32_t)__builtin_amdgcn_readlane((int)mycode, (int)e);
-      uint32_t pos = (uint32_t)__builtin_amdgcn_readlane((int)mypos, (int)e);
-      if (sp > 0 && (code & 255u) == (top & 255u)) {              // grow: H =:= Close (:806-807)
-        if ((uint32_t)l == nclose) { cs = top >> 8; cp = pos; }
-        nclose++;
-        sp--;
-        if (sp > 0) {
-          if (sp == sbase) {                                      // refill the lower 32 entries from the spill area
-            uint32_t up = (uint32_t)__shfl_up((int)stk, 32);
-            sbase -= 32;
-            stk = l < 32 ? spill[sbase + l] : up;
-          }
-          top = (uint32_t)__builtin_amdgcn_readlane((int)stk, (int)(sp - 1 - sbase));
+  uint32_t top = 0;                      // copy of the top entry
+  uint32_t orank = 0;                    // opener events before eb
+  auto rs_refill = [&]() {               // sp == sbase > 0: the lower 32 entries come back from the spill area
+    uint32_t up = (uint32_t)__shfl_up((int)stk, 32);
+    sbase -= 32;
+    stk = l < 32 ? spill[sbase + l] : up;
+  };
+  auto rs_spill = [&]() {                // the lower half goes to the spill area
+    if (l < 32) spill[sbase + l] = stk;
+    stk = (uint32_t)__shfl_down((int)stk, 32);
+    sbase += 32;
+  };
+  auto rs_pop = [&]() {                  // sp > 0
+    sp--;
+    if (sp > 0) {
+      if (sp == sbase) rs_refill();
+      top = (uint32_t)__builtin_amdgcn_readlane((int)stk, (int)(sp - 1 - sbase));
+    }
+  };
+  auto rs_push = [&](uint32_t ent) {
+    if (sp - sbase == 64) rs_spill();
+    if ((uint32_t)l == sp - sbase) stk = ent;
+    top = ent; sp++;
+  };
+  const bool lanes_on = !(c.p->flags & EH_FLAG_TREE_NO_LANES) && nev >= 8 * TL_S;
+  uint32_t seq_left = 0, seq_len = TL_SEQ_MIN;
+  uint32_t nlane = 0;                    // events decided by lane batches (statistics)
+  if (lanes_on) { TL_COUNT(3, 1); TL_COUNT(4, nev); }
+  uint32_t eb = 0;
+  while (eb < nev) {
+    // (wave-uniform all of them, and said so: without it the compiler keeps the real stack's depth and top in vector registers and
+    // turns every decision of the sequential loop into an exec-mask branch)
+    eb = uni(eb); sp = uni(sp); sbase = uni(sbase); top = uni(top); orank = uni(orank); seq_left = uni(seq_left); seq_len = uni(seq_len);
+    if (!lanes_on || seq_left > 0 || nev - eb < TL_TAIL) {
+      // the sequential loop: 64 events, delimiter codes in registers (lane i = event i of the batch)
+      uint32_t mycode = eb + (uint32_t)l < nev ? DelimCls()((uint32_t)H[evp[eb + l]]) : 0;
+      // bit 8: opener; bits 16..23: the closer code an opener waits for
+      mycode |= delim_is_opener(mycode) ? (0x100u | (delim_close_code(mycode) << 16)) : 0u;
+      uint32_t cnt = nev - eb < 64 ? nev - eb : 64;
+      const unsigned long long opm = __ballot((mycode & 0x100u) != 0);
+      uint32_t npush = 0, nclose = 0;
+      uint32_t ps = 0, po = 0, pp = 0, cs = 0, cp = 0;
+      for (uint32_t e = 0; e < cnt; e++) {
+        uint32_t code = (uint32_t)__builtin_amdgcn_readlane((int)mycode, (int)e);
+        const uint32_t pos = eb + e;
+        if (sp > 0 && (code & 255u) == (top & 255u)) {              // grow: H =:= Close (:806-807)
+          if ((uint32_t)l == nclose) { cs = top >> 8; cp = pos; }
+          nclose++;
+          rs_pop();
+        } else if (code & 0x100u) {
+          uint32_t parent = sp > 0 ? (top >> 8) : 0xFFFFFFFFu;
+          uint32_t slot = orank + (uint32_t)__popcll(opm & ((1ull << e) - 1));
+          if ((uint32_t)l == npush) { ps = slot; po = pos; pp = parent; }
+          npush++;
+          rs_push((slot << 8) | (code >> 16));
         }
-      } else if (code & 0x100u) {
-        if (sp - sbase == 64) {                                   // spill the lower half
-          if (l < 32) spill[sbase + l] = stk;
-          stk = (uint32_t)__shfl_down((int)stk, 32);
-          sbase += 32;
+      }
+      if ((uint32_t)l < npush) { tab[ps].open = po; tab[ps].pend = pp; }
+      if ((uint32_t)l < nclose) tab[cs].close = cp;
+      orank += (uint32_t)__popcll(opm);
+      eb += cnt;
+      seq_left = seq_left > cnt ? seq_left - cnt : 0;
+      continue;
+    }
+    // ---- a lane batch: events [eb, eb + 64 * TL_S)
+    lanes_sync();                                                  // the previous batch is done with the LDS arrays
+    // codes of the batch's events into LDS (coalesced loads of the positions, 8 gathers in flight)
+    for (uint32_t t0 = 0; t0 < TL_S; t0 += 8) {
+      uint32_t bb[8];
+#pragma unroll
+      for (uint32_t u = 0; u < 8; u++) { uint32_t idx = eb + (t0 + u) * 64 + (uint32_t)l; bb[u] = idx < nev ? evp[idx] : 0xFFFFFFFFu; }
+#pragma unroll
+      for (uint32_t u = 0; u < 8; u++) bb[u] = bb[u] != 0xFFFFFFFFu ? DelimCls()((uint32_t)H[bb[u]]) : 0u;
+#pragma unroll
+      for (uint32_t u = 0; u < 8; u++) { uint32_t e = (t0 + u) * 64 + (uint32_t)l; tl_bytes()[4 * TL_COD + (e / TL_S) * TL_SP + e % TL_S] = (uint8_t)bb[u]; }
+    }
+    lanes_sync();
+    // lane phase: the machine over my run, from an empty local stack
+    uint32_t om = 0, cm = 0, em = 0;       // events of my run that are openers / complete a local node / are escaping closers
+    uint32_t d = 0, tc = 0, tj = 0;        // local depth; closer code and event of the local top
+    uint32_t stopj = TL_S;
+    uint32_t ne = 0;                       // my escaping closers so far
+    bool ord = false;                      // a node opened at my depth 0 behind an escaping closer: its parent needs the walk's tops
+    uint32_t kn = l == 0 ? (sp > 0 ? (top & 255u) : 0u) : 255u;   // the real top's closer code while I know it (0: real stack empty; 255: unknown)
+    {
+      const uint32_t cb = 4 * TL_COD + (uint32_t)l * TL_SP, lb = 4 * TL_LNK + (uint32_t)l * TL_SP, xb = 4 * TL_ESC + (uint32_t)l * TL_SP;
+      for (uint32_t j = 0; j < TL_S; j++) {
+        const uint32_t cd = tl_bytes()[cb + j];
+        if (cd == 0) continue;
+        const uint32_t bit = 1u << j;
+        const bool isop = delim_is_opener(cd);
+        if (isop) om |= bit;
+        if (stopj < TL_S) continue;                                  // stopped: the walk decides the rest of my run
+        bool push = false;
+        if (d > 0) {
+          if (cd == tc) {
+            tl_bytes()[lb + j] = (uint8_t)tj; cm |= bit; d--;
+            if (d > 0) { uint32_t en = tl_stack()[(d - 1) * 64 + (uint32_t)l]; tc = en & 15u; tj = en >> 4; }
+          } else push = isop;
+        } else if (cd >= 9) {                                        // a quote, my stack empty
+          if (kn == 255u) { stopj = j; continue; }
+          if (kn == cd) { em |= bit; tl_bytes()[xb + ne++] = (uint8_t)j; kn = 255u; }   // closes the real top: the walk pops it
+          else push = true;
+        } else if (isop) push = true;
+        else { em |= bit; tl_bytes()[xb + ne++] = (uint8_t)j; if (kn == cd) kn = 255u; }
+        if (push) {
+          if (d == 0 && em != 0) ord = true;
+          tl_bytes()[lb + j] = d > 0 ? (uint8_t)tj : (uint8_t)255;
+          tc = delim_close_code(cd); tj = j;
+          tl_stack()[d * 64 + (uint32_t)l] = (uint16_t)((j << 4) | tc);
+          d++;
         }
-        uint32_t parent = sp > 0 ? (top >> 8) : 0xFFFFFFFFu;
-        uint32_t ent = (nslots << 8) | (code >> 16);
-        if ((uint32_t)l == sp - sbase) stk = ent;
-        if ((uint32_t)l == npush) { po = pos; pp = parent; }
-        npush++;
-        top = ent; nslots++; sp++;
       }
     }
-    if ((uint32_t)l < npush) { tab[first + l].open = po; tab[first + l].pend = pp; }
-    if ((uint32_t)l < nclose) tab[cs].close = cp;
+    lanes_sync();
+    const uint32_t oinc = wave_incl_scan((uint32_t)__popc(om));
+    const uint32_t obase = orank + oinc - (uint32_t)__popc(om);                  // slot of my run's first opener event
+    const uint32_t committed = nev - eb < 64 * TL_S ? nev - eb : 64 * TL_S;
+    uint32_t nseq = 0;                                             // events of the batch the walk decided one by one
+    // walk: lanes with escaping closers, unclosed openers or a stop, in order, against the real stack
+    const uint32_t top0 = sp > 0 ? top >> 8 : 0xFFFFFFFFu;
+    uint32_t topin = top0, topout = top0;                          // real top slot when my run begins / ends
+    unsigned long long im = __ballot(em != 0 || d > 0 || stopj < TL_S);
+    const unsigned long long ordm = __ballot(ord);
+    const unsigned long long items = im;
+    uint32_t npush = 0, nclose = 0;
+    uint32_t ps = 0, pe = 0, pp = 0, cs = 0, ce = 0;               // buffered pushes (slot, event, parent) and closes (slot, event)
+    auto w_flush = [&]() {
+      if ((uint32_t)l < npush) { tab[ps].open = pe; tab[ps].pend = pp; }
+      if ((uint32_t)l < nclose) tab[cs].close = ce;
+      npush = 0; nclose = 0;
+    };
+    while (im) {
+      const int k = (int)__builtin_ctzll(im); im &= im - 1;
+      uint32_t ekm = (uint32_t)__builtin_amdgcn_readlane((int)em, k);
+      const uint32_t okm = (uint32_t)__builtin_amdgcn_readlane((int)om, k), ob = (uint32_t)__builtin_amdgcn_readlane((int)obase, k);
+      const uint32_t dk = (uint32_t)__builtin_amdgcn_readlane((int)d, k), sj = (uint32_t)__builtin_amdgcn_readlane((int)stopj, k);
+      const uint32_t ev0 = eb + (uint32_t)k * TL_S;
+      uint32_t cur = sp > 0 ? top >> 8 : 0xFFFFFFFFu;
+      if (l == k) topin = cur;
+      if (ekm && !((ordm >> k) & 1ull)) {
+        // the run's escaping closers, in bulk: lane t holds the t-th of them; closers c0, c0 + 1, ... are compared with the top
+        // entry, the one below, ... all at once, and the whole matching prefix is popped; the closer behind it met an entry
+        // it does not close and is ignored.  (No node of this run needs the tops in between.)
+        const uint32_t m = (uint32_t)__popc(ekm);
+        const uint32_t my_j = (uint32_t)l < m ? (uint32_t)tl_bytes()[4 * TL_ESC + (uint32_t)k * TL_SP + (uint32_t)l] : 0u;
+        const uint32_t my_c = (uint32_t)l < m ? (uint32_t)tl_bytes()[4 * TL_COD + (uint32_t)k * TL_SP + my_j] : 0u;
+        uint32_t c0 = 0;
+        while (c0 < m && sp > 0) {
+          if (sp == sbase) rs_refill();
+          const uint32_t avail = sp - sbase;
+          const uint32_t cc = (uint32_t)__shfl((int)my_c, (int)((c0 + (uint32_t)l) & 63u)), cj = (uint32_t)__shfl((int)my_j, (int)((c0 + (uint32_t)l) & 63u));
+          const uint32_t en = (uint32_t)__shfl((int)stk, (int)((avail - 1 - (uint32_t)l) & 63u));
+          const bool ok = c0 + (uint32_t)l < m && (uint32_t)l < avail && cc == (en & 255u);
+          const unsigned long long nok = ~__ballot(ok);
+          const uint32_t r = nok ? (uint32_t)__builtin_ctzll(nok) : 64u;
+          if ((uint32_t)l < r) tab[en >> 8].close = ev0 + cj;
+          sp -= r; c0 += r;
+          if (c0 < m && r < avail) c0++;
+        }
+        if (sp > 0) { if (sp == sbase) rs_refill(); top = (uint32_t)__builtin_amdgcn_readlane((int)stk, (int)(sp - 1 - sbase)); }
+        cur = sp > 0 ? top >> 8 : 0xFFFFFFFFu;
+        ekm = 0;
+      }
+      uint32_t e = 0;
+      while (ekm) {                                                // one by one, keeping the top after each (TL_TOP)
+        const uint32_t j = (uint32_t)__builtin_ctz(ekm); ekm &= ekm - 1;
+        const uint32_t cd = uni((uint32_t)tl_bytes()[4 * TL_COD + (uint32_t)k * TL_SP + j]);
+        if (sp > 0 && cd == (top & 255u)) {
+          if ((uint32_t)l == nclose) { cs = top >> 8; ce = ev0 + j; }
+          nclose++;
+          rs_pop();
+          cur = sp > 0 ? top >> 8 : 0xFFFFFFFFu;
+          if (nclose == 64) w_flush();
+        }
+        if (l == 0) g_fuse_lds[TL_TOP + (uint32_t)k * TL_S + e] = cur;
+        e++;
+      }
+      if (dk > 0) {
+        // the run's unclosed openers go onto the real stack together: entry i into the lane that holds depth sp + i
+        if (sp - sbase + dk > 64) rs_spill();
+        const uint32_t at = sp - sbase, i = (uint32_t)l - at;
+        const bool in = (uint32_t)l >= at && i < dk;
+        const uint32_t en = in ? (uint32_t)tl_stack()[i * 64 + (uint32_t)k] : 0u;
+        const uint32_t enp = (in && i > 0) ? (uint32_t)tl_stack()[(i - 1) * 64 + (uint32_t)k] : 0u;
+        const uint32_t j = en >> 4, slot = ob + (uint32_t)__popc(okm & ((1u << j) - 1));
+        if (in) {
+          stk = (slot << 8) | (en & 15u);
+          tab[slot].open = ev0 + j; tab[slot].pend = i > 0 ? ob + (uint32_t)__popc(okm & ((1u << (enp >> 4)) - 1)) : cur;
+        }
+        sp += dk;
+        top = (uint32_t)__builtin_amdgcn_readlane((int)stk, (int)(sp - 1 - sbase));
+        cur = top >> 8;
+      }
+      if (sj < TL_S) {
+        // the run stopped at a quote: that quote and the rest of the run, one event after the other against the real stack
+        // (lane i = event sj + i; the runs of the lanes behind are summaries of their own events and stay valid)
+        const uint32_t rem = TL_S - sj;
+        uint32_t mc = (uint32_t)l < rem ? (uint32_t)tl_bytes()[4 * TL_COD + (uint32_t)k * TL_SP + sj + (uint32_t)l] : 0u;
+        mc |= delim_is_opener(mc) ? (0x100u | (delim_close_code(mc) << 16)) : 0u;
+        const unsigned long long opm = __ballot((mc & 0x100u) != 0);
+        const uint32_t rb = ob + (uint32_t)__popc(okm & ((1u << sj) - 1));
+        for (uint32_t e2 = 0; e2 < rem; e2++) {
+          const uint32_t code = (uint32_t)__builtin_amdgcn_readlane((int)mc, (int)e2);
+          if (sp > 0 && (code & 255u) == (top & 255u)) {
+            if ((uint32_t)l == nclose) { cs = top >> 8; ce = ev0 + sj + e2; }
+            nclose++;
+            rs_pop();
+            if (nclose == 64) w_flush();
+          } else if (code & 0x100u) {
+            const uint32_t parent = sp > 0 ? top >> 8 : 0xFFFFFFFFu;
+            const uint32_t slot = rb + (uint32_t)__popcll(opm & ((1ull << e2) - 1));
+            if ((uint32_t)l == npush) { ps = slot; pe = ev0 + sj + e2; pp = parent; }
+            npush++;
+            rs_push((slot << 8) | (code >> 16));
+            if (npush == 64) w_flush();
+          }
+        }
+        nseq += rem;
+      }
+      if (l == k) topout = sp > 0 ? top >> 8 : 0xFFFFFFFFu;
+    }
+    w_flush();
+    lanes_sync();
+    // the nodes my run completed: slot, ends and parent (the real top of the moment for a node opened at local depth 0)
+    {
+      const unsigned long long below = items & ((1ull << l) - 1);
+      const uint32_t t = (uint32_t)__shfl((int)topout, below ? 63 - (int)__builtin_clzll(below) : 0);
+      if (!((items >> l) & 1ull)) topin = below ? t : top0;
+    }
+    {
+      const uint32_t lb = 4 * TL_LNK + (uint32_t)l * TL_SP, ev0 = eb + (uint32_t)l * TL_S;
+      uint32_t m = cm;
+      while (m) {
+        const uint32_t j = (uint32_t)__builtin_ctz(m); m &= m - 1;
+        const uint32_t jo = tl_bytes()[lb + j], lp = tl_bytes()[lb + jo];
+        const uint32_t slot = obase + (uint32_t)__popc(om & ((1u << jo) - 1));
+        uint32_t par;
+        if (lp != 255u) par = obase + (uint32_t)__popc(om & ((1u << lp) - 1));
+        else { const uint32_t e = (uint32_t)__popc(em & ((1u << jo) - 1)); par = e ? g_fuse_lds[TL_TOP + (uint32_t)l * TL_S + e - 1] : topin; }
+        tab[slot].open = ev0 + jo; tab[slot].close = ev0 + j; tab[slot].pend = par;
+      }
+    }
+    orank += (uint32_t)__builtin_amdgcn_readlane((int)oinc, 63);
+    eb += committed;
+    nlane += committed - nseq; TL_COUNT(0, committed - nseq); TL_COUNT(1, 1);
+    if (2 * nseq > committed) { TL_COUNT(2, 1); seq_left = seq_len; if (seq_len < TL_SEQ_MAX) seq_len *= 2; }
+    else if (seq_len > TL_SEQ_MIN) seq_len /= 2;
   }
   wave_sync();
-  TR_PH(12); TR_ST(16, nslots);
-  // level end of every slot: one past the close of the nearest ancestor that did close (L at top level).
+  TR_PH(12);
+#ifdef EH_PROF
+  // eh_result_prof slot 85: events, parses (above); slot 86: events decided by lane batches, quotes among the events
+  if (l == 0) { atomicAdd(&c.p->prof[2 * 86], (unsigned long long)nlane); atomicAdd(&c.p->prof[2 * 86 + 1], (unsigned long long)nquote); }
+#endif
+  (void)nlane; (void)nquote;
+  // level end of every node: one past the close of the nearest ancestor that did close (L at top level).
   // An opener that never closes stays on the matcher's stack for good, and so does everything below
   // it: the ancestors of an unclosed slot are all unclosed.  So the level end is close[parent] + 1 if
   // the parent closed and L otherwise — one gather (before the in-place compaction moves slots).
-  for (uint32_t i = (uint32_t)l; i < nslots; i += 64) {
+  // (Only completed nodes are looked at: a slot that never closed, or was never used, is dropped below.)
+  for (uint32_t i = (uint32_t)l; i < nopen; i += 64) {
+    if (tab[i].close == 0xFFFFFFFFu) continue;
     uint32_t par = tab[i].pend, pe = L;
-    if (par != 0xFFFFFFFFu) { uint32_t pc = tab[par].close; if (pc != 0xFFFFFFFFu) pe = pc + 1; }
+    if (par != 0xFFFFFFFFu) { uint32_t pc = tab[par].close; if (pc != 0xFFFFFFFFu) pe = evp[pc] + 1; }
     tab[i].pad = pe;
   }
   wave_sync();
   TR_PH(13);
   // compact completed nodes (keep pre-order); pend <- level end
   uint32_t n = 0;
-  for (uint32_t base = 0; base < nslots; base += 64) {
+  for (uint32_t base = 0; base < nopen; base += 64) {
     uint32_t i = base + (uint32_t)l;
     TNode t{0, 0xFFFFFFFFu, 0, 0};
-    if (i < nslots) t = tab[i];
-    bool ok = i < nslots && t.close != 0xFFFFFFFFu;
+    if (i < nopen) t = tab[i];
+    bool ok = i < nopen && t.close != 0xFFFFFFFFu;
     unsigned long long m = __ballot(ok);
     uint32_t before = (uint32_t)__popcll(m & ((1ull << l) - 1));
     wave_sync();
-    if (ok) { t.pend = t.pad; tab[n + before] = t; }   // n + before <= i: never overwrites an unread slot of a later chunk
+    if (ok) { t.open = evp[t.open]; t.close = evp[t.close]; t.pend = t.pad; tab[n + before] = t; }   // n + before <= i: never overwrites an unread slot of a later chunk
     n += (uint32_t)__popcll(m);
     wave_sync();
   }

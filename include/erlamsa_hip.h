@@ -118,6 +118,8 @@ typedef struct eh_options {
 
 #define EH_FLAG_NO_COOP 64u        /* diagnostic: every case does all of its work on its own wavefront (no cooperative execution of
                                      the bulk loops of heavy cases, csrc/eh_common.h CoBoard; ABI 8).  Same bytes either way. */
+#define EH_FLAG_TREE_NO_LANES 128u /* diagnostic: the delimiter matcher of the tree mutators decides every event in its sequential loop instead
+                                     of 64 runs of events at a time, one run per lane (csrc/eh_tree.h); results are identical */
 #define EH_FLAG_ORDERED_OUTPUT 1u /* compact the output arena into case order after the batch */
 #define EH_FLAG_META_TRACE 2u     /* keep every case's meta trace (eh_result_meta) */
 #define EH_FLAG_SGML_NO_LANES 32u  /* diagnostic: the sgm tokenizer makes its tag attempts one after the other instead of 64 at a time, one per
