@@ -9,6 +9,8 @@ Option keys are the reference's Dict keys (erlamsa_main.erl:127-163):
   input       bytes                              (paths = [direct])
   blockscale  float
   skip        cases numbered <= skip are computed but dropped (erlamsa_main.erl:161,191-196)
+  unique      (not the reference's: radamsa's --hash) duplicates are found on the device and only one copy of every distinct output
+              is downloaded; fuzzer/1 returns the distinct results in first-occurrence order
 Only `paths => [direct]`, `output => return` is served by the GPU path.  Keys the reference honours and a batch
 on the GPU cannot - external_mutations (custom mutator funs appended to the table, erlamsa_main.erl:128), external_post (a
 post-processor applied per written block, :159), sequence_muta (:223-235) - raise Unsupported: the caller routes that run to
@@ -98,8 +100,16 @@ def fuzz_batch(inputs, opts=None, return_status=False, device=0):
     data, off = pack_corpus(list(inputs))
     eng.upload_corpus(data, off)
     eng.fuzz_batch(seed=_seed_of(opts), first_case=int(opts.get("first_case", 1)), n=len(inputs))
-    outs, status = eng.download()
-    return (outs, status) if return_status else outs
+    if not opts.get("unique"):
+        outs, status = eng.download()
+        return (outs, status) if return_status else outs
+    # one copy of every distinct output crosses PCIe; the other cases share its bytes object
+    first_of, _, _ = eng.unique()
+    status = eng.status()
+    reps = np.flatnonzero(first_of == np.arange(len(first_of), dtype=np.uint64))
+    got = dict(zip(reps.tolist(), eng.download_select(reps)))
+    outs = [got[int(f)] for f in first_of]
+    return (outs, status, first_of) if return_status else outs
 
 
 class EngineLimit(RuntimeError):
@@ -115,7 +125,8 @@ def fuzzer(opts):
     """erlamsa_main:fuzzer/1 for paths=[direct], output=return: the same input N times.
     Like record_result/2 (erlamsa_main.erl:120-122) empty results are dropped (a crashed worker, status 1, gives <<>>).
     A case that stopped at an engine-only limit is never dropped silently: EngineLimit is raised unless
-    opts["on_engine_limit"] == "skip" (then the caller reads the statuses through fuzz_batch(return_status=True))."""
+    opts["on_engine_limit"] == "skip" (then the caller reads the statuses through fuzz_batch(return_status=True)).
+    opts["unique"]: the distinct results, each where it first occurs among the cases that are kept."""
     opts = dict(opts)
     if opts.get("paths", ["direct"]) != ["direct"] or opts.get("output", "return") != "return":
         raise ValueError("only paths=[direct], output=return is served by the GPU path")
@@ -123,13 +134,17 @@ def fuzzer(opts):
         raise Unsupported(host_only(opts))
     n = int(opts.get("n", 1))
     skip, first = int(opts.get("skip", 0)), int(opts.get("first_case", 1))
-    outs, status = fuzz_batch([bytes(opts.get("input", b""))] * n, opts, return_status=True, device=int(opts.get("device", 0)))
-    res, limited = [], []
+    got = fuzz_batch([bytes(opts.get("input", b""))] * n, opts, return_status=True, device=int(opts.get("device", 0)))
+    outs, status = got[0], got[1]
+    first_of = got[2] if opts.get("unique") else range(n)       # without the filter every case is its own first
+    res, limited, seen = [], [], set()
     for i, (o, s) in enumerate(zip(outs, status)):
         if first + i <= skip:                                   # `I =< Skip` (erlamsa_main.erl:191): written to the skip port, which keeps nothing
             continue
         if s == CASE_OK and len(o) > 0:
-            res.append(o)
+            if int(first_of[i]) not in seen:
+                seen.add(int(first_of[i]))
+                res.append(o)
         elif s >= 2:
             limited.append((i, int(s)))
     if limited and opts.get("on_engine_limit", "raise") != "skip":

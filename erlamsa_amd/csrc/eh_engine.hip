@@ -38,6 +38,7 @@
 #include "eh_json.h"
 #include "eh_zlib.h"
 #include "eh_zip.h"
+#include "eh_unique.h"
 #include "eh_comm.h"
 
 namespace eh {
@@ -1222,6 +1223,12 @@ struct eh_ctx {
   hipStream_t own_stream = nullptr;                     // eh_stream: a stream of the context's own (non-blocking), made on first request
   uint64_t last_n = 0, last_in_bytes = 0;
   bool have_result = false;
+  // uniqueness filter (eh_unique.h): sized on first use, reused while they fit; results are cached per batch (batch_seq)
+  uint64_t* d_uq_digest = nullptr; uint64_t* d_uq_first = nullptr; uint64_t* d_uq_pfirst = nullptr; uint32_t* d_uq_flag = nullptr; uint64_t uq_case_cap = 0;
+  unsigned long long* d_uq_term = nullptr; uint64_t uq_term_cap = 0;         // a pair of CRCs per piece
+  unsigned long long* d_uq_tab = nullptr; uint64_t uq_tab_cap = 0;           // [0] unique cases, [1] their bytes, then owner[slots], rep[slots]
+  uint64_t uq_digest_seq = 0, uq_unique_seq = 0, uq_n_unique = 0, uq_bytes = 0;   // batch the device arrays / the two totals belong to (0: none)
+  uint64_t* d_sel = nullptr; uint64_t sel_cap = 0;                           // eh_result_download_select: offsets, lengths, destinations of the listed cases
 };
 
 #define HIPCHK(ctx, call)                                                                             \
@@ -1598,6 +1605,8 @@ void eh_destroy(eh_ctx* ctx) {
   if (ctx->d_params) (void)hipFree(ctx->d_params);
   if (ctx->d_out2) (void)hipFree(ctx->d_out2);
   if (ctx->d_ord) (void)hipFree(ctx->d_ord);
+  (void)hipFree(ctx->d_uq_digest); (void)hipFree(ctx->d_uq_first); (void)hipFree(ctx->d_uq_pfirst); (void)hipFree(ctx->d_uq_flag);
+  (void)hipFree(ctx->d_uq_term); (void)hipFree(ctx->d_uq_tab); (void)hipFree(ctx->d_sel);
   if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
   if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
   delete ctx;
@@ -2137,6 +2146,51 @@ int eh_result_occupancy(eh_ctx* ctx, uint64_t* out /* 5 values */) {
   out[4] = (uint64_t)ctx->cus * 4u * EH_WAVES_PER_SIMD;
   return EH_OK;
 }
+// The download pipeline of eh_result_download and eh_result_download_select: item k (a case) is d_soff[k] .. + d_slen[k] of the arena and
+// goes to data + ord[k]; d_dst is ord (n + 1 entries) in device memory.  Chunks of consecutive items are gathered on the device into two
+// bounce buffers; chunk k goes over PCIe (full rate when `data` is pinned or registered host memory) while chunk k + 1 is gathered.
+static int gather_download(eh_ctx* ctx, uint8_t* data, uint64_t n, const uint64_t* d_soff, const uint64_t* d_slen, const uint64_t* d_dst,
+                           const std::vector<uint64_t>& ord, uint64_t maxlen) {
+  const uint64_t total = ord[n];
+  if (total == 0) return EH_OK;
+  uint64_t chunk = ctx->dl_chunk < 64 ? 64 : ctx->dl_chunk;        // eh_options.download_chunk_bytes
+  uint64_t want = maxlen > chunk ? maxlen : chunk;
+  if (want > total) want = total;
+  want = (want + 4095) & ~4095ull;
+  if (!ctx->dl_gather) {
+    HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->dl_gather, hipStreamNonBlocking));
+    HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->dl_copy, hipStreamNonBlocking));
+    for (int k = 0; k < 2; k++) { HIPCHK(ctx, hipEventCreate(&ctx->ev_g[k])); HIPCHK(ctx, hipEventCreate(&ctx->ev_c[k])); }
+  }
+  if (ctx->bounce_cap < want || ctx->bounce_chunk != chunk) {
+    for (int k = 0; k < 2; k++) { if (ctx->d_bounce[k]) (void)hipFree(ctx->d_bounce[k]); ctx->d_bounce[k] = nullptr; }
+    ctx->bounce_cap = 0;
+    for (int k = 0; k < 2; k++) HIPCHK(ctx, hipMalloc(&ctx->d_bounce[k], want));
+    ctx->bounce_cap = want; ctx->bounce_chunk = chunk;
+  }
+  uint64_t a = 0; int k = 0;
+  while (a < n) {
+    uint64_t b = a + 1;
+    while (b < n && ord[b + 1] - ord[a] <= ctx->bounce_cap) b++;
+    const int buf = k & 1;
+    if (k >= 2) HIPCHK(ctx, hipStreamWaitEvent(ctx->dl_gather, ctx->ev_c[buf], 0));     // the copy that last read this buffer
+    uint64_t bytes = ord[b] - ord[a];
+    if (bytes) {
+      uint64_t cnt = b - a;
+      uint32_t g = (uint32_t)ctx->cus * 32u; if (g > cnt) g = (uint32_t)cnt;
+      hipLaunchKernelGGL(eh_order_gather_kernel, dim3(g), dim3(64), 0, ctx->dl_gather, (const uint8_t*)ctx->d_out, ctx->d_bounce[buf],
+                         (const uint64_t*)(d_soff + a), (const uint64_t*)(d_slen + a), (const uint64_t*)(d_dst + a), cnt, ord[a]);
+    }
+    HIPCHK(ctx, hipEventRecord(ctx->ev_g[buf], ctx->dl_gather));
+    HIPCHK(ctx, hipStreamWaitEvent(ctx->dl_copy, ctx->ev_g[buf], 0));
+    if (bytes) HIPCHK(ctx, hipMemcpyAsync(data + ord[a], ctx->d_bounce[buf], bytes, hipMemcpyDeviceToHost, ctx->dl_copy));
+    HIPCHK(ctx, hipEventRecord(ctx->ev_c[buf], ctx->dl_copy));
+    a = b; k++;
+  }
+  HIPCHK(ctx, hipStreamSynchronize(ctx->dl_copy));
+  HIPCHK(ctx, hipGetLastError());
+  return EH_OK;
+}
 int eh_result_download(eh_ctx* ctx, uint8_t* data, uint64_t cap, uint64_t* off, int32_t* status) {
   if (!ctx) return EH_E_INVALID;
   if (!ctx->have_result) { ctx->err = "no batch has run"; return EH_E_STATE; }
@@ -2153,25 +2207,9 @@ int eh_result_download(eh_ctx* ctx, uint8_t* data, uint64_t cap, uint64_t* off, 
       if (total) HIPCHK(ctx, hipMemcpy(data, ctx->d_out, total, hipMemcpyDeviceToHost));
       return EH_OK;
     }
-    // completion-ordered arena -> case order: gather a chunk of consecutive cases into a bounce buffer on the device,
-    // copy it out (full PCIe rate when `data` is pinned or registered host memory) while the next chunk is gathered
+    // completion-ordered arena -> case order (gather_download)
     if (total == 0) return EH_OK;
     uint64_t maxlen = 0; for (uint64_t i = 0; i < n; i++) if (len[i] > maxlen) maxlen = len[i];
-    uint64_t chunk = ctx->dl_chunk < 64 ? 64 : ctx->dl_chunk;        // eh_options.download_chunk_bytes
-    uint64_t want = maxlen > chunk ? maxlen : chunk;
-    if (want > total) want = total;
-    want = (want + 4095) & ~4095ull;
-    if (!ctx->dl_gather) {
-      HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->dl_gather, hipStreamNonBlocking));
-      HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->dl_copy, hipStreamNonBlocking));
-      for (int k = 0; k < 2; k++) { HIPCHK(ctx, hipEventCreate(&ctx->ev_g[k])); HIPCHK(ctx, hipEventCreate(&ctx->ev_c[k])); }
-    }
-    if (ctx->bounce_cap < want || ctx->bounce_chunk != chunk) {
-      for (int k = 0; k < 2; k++) { if (ctx->d_bounce[k]) (void)hipFree(ctx->d_bounce[k]); ctx->d_bounce[k] = nullptr; }
-      ctx->bounce_cap = 0;
-      for (int k = 0; k < 2; k++) HIPCHK(ctx, hipMalloc(&ctx->d_bounce[k], want));
-      ctx->bounce_cap = want; ctx->bounce_chunk = chunk;
-    }
     if (!ctx->d_ord || ctx->ord_cap < n + 1) {
       if (ctx->d_ord) (void)hipFree(ctx->d_ord);
       ctx->d_ord = nullptr;
@@ -2181,27 +2219,7 @@ int eh_result_download(eh_ctx* ctx, uint8_t* data, uint64_t cap, uint64_t* off, 
     std::vector<uint64_t> ord(n + 1);
     { uint64_t p = 0; for (uint64_t i = 0; i < n; i++) { ord[i] = p; p += len[i]; } ord[n] = p; }
     HIPCHK(ctx, hipMemcpy(ctx->d_ord, ord.data(), (n + 1) * 8, hipMemcpyHostToDevice));
-    uint64_t a = 0; int k = 0;
-    while (a < n) {
-      uint64_t b = a + 1;
-      while (b < n && ord[b + 1] - ord[a] <= ctx->bounce_cap) b++;
-      const int buf = k & 1;
-      if (k >= 2) HIPCHK(ctx, hipStreamWaitEvent(ctx->dl_gather, ctx->ev_c[buf], 0));     // the copy that last read this buffer
-      uint64_t bytes = ord[b] - ord[a];
-      if (bytes) {
-        uint64_t cnt = b - a;
-        uint32_t g = (uint32_t)ctx->cus * 32u; if (g > cnt) g = (uint32_t)cnt;
-        hipLaunchKernelGGL(eh_order_gather_kernel, dim3(g), dim3(64), 0, ctx->dl_gather, (const uint8_t*)ctx->d_out, ctx->d_bounce[buf],
-                           (const uint64_t*)(ctx->d_off + a), (const uint64_t*)(ctx->d_len + a), (const uint64_t*)(ctx->d_ord + a), cnt, ord[a]);
-      }
-      HIPCHK(ctx, hipEventRecord(ctx->ev_g[buf], ctx->dl_gather));
-      HIPCHK(ctx, hipStreamWaitEvent(ctx->dl_copy, ctx->ev_g[buf], 0));
-      if (bytes) HIPCHK(ctx, hipMemcpyAsync(data + ord[a], ctx->d_bounce[buf], bytes, hipMemcpyDeviceToHost, ctx->dl_copy));
-      HIPCHK(ctx, hipEventRecord(ctx->ev_c[buf], ctx->dl_copy));
-      a = b; k++;
-    }
-    HIPCHK(ctx, hipStreamSynchronize(ctx->dl_copy));
-    HIPCHK(ctx, hipGetLastError());
+    return gather_download(ctx, data, n, ctx->d_off, ctx->d_len, ctx->d_ord, ord, maxlen);
   }
   return EH_OK;
 }
@@ -2423,6 +2441,150 @@ int eh_last_kernel_ms(eh_ctx* ctx, float* ms) {
   if (!ctx->have_result) { ctx->err = "no batch has run"; return EH_E_STATE; }
   HIPCHK(ctx, hipEventSynchronize(ctx->ev1));
   HIPCHK(ctx, hipEventElapsedTime(ms, ctx->ev0, ctx->ev1));
+  return EH_OK;
+}
+
+// ---- uniqueness filter (csrc/eh_unique.h) -----------------------------------------------------------------------------------------
+static_assert(UQ_PIECE == EH_UNIQUE_PIECE_BYTES, "the header documents the piece size");
+// Device buffers for n cases and up to `pieces` pieces; they belong to the context and are reused while they fit.
+static int uq_ensure(eh_ctx* ctx, uint64_t n, uint64_t pieces, uint64_t slots) {
+  if (n > ctx->uq_case_cap) {
+    (void)hipFree(ctx->d_uq_digest); (void)hipFree(ctx->d_uq_first); (void)hipFree(ctx->d_uq_pfirst); (void)hipFree(ctx->d_uq_flag);
+    ctx->d_uq_digest = ctx->d_uq_first = ctx->d_uq_pfirst = nullptr; ctx->d_uq_flag = nullptr; ctx->uq_case_cap = 0;
+    HIPCHK(ctx, hipMalloc(&ctx->d_uq_digest, n * 8));
+    HIPCHK(ctx, hipMalloc(&ctx->d_uq_first, n * 8));
+    HIPCHK(ctx, hipMalloc(&ctx->d_uq_pfirst, (n + 1) * 8));
+    HIPCHK(ctx, hipMalloc(&ctx->d_uq_flag, n * 4));
+    ctx->uq_case_cap = n;
+  }
+  if (pieces > ctx->uq_term_cap) {
+    (void)hipFree(ctx->d_uq_term); ctx->d_uq_term = nullptr; ctx->uq_term_cap = 0;
+    HIPCHK(ctx, hipMalloc(&ctx->d_uq_term, pieces * 8));
+    ctx->uq_term_cap = pieces;
+  }
+  if (2 + 2 * slots > ctx->uq_tab_cap) {
+    (void)hipFree(ctx->d_uq_tab); ctx->d_uq_tab = nullptr; ctx->uq_tab_cap = 0;
+    HIPCHK(ctx, hipMalloc(&ctx->d_uq_tab, (2 + 2 * slots) * 8));
+    ctx->uq_tab_cap = 2 + 2 * slots;
+  }
+  return EH_OK;
+}
+static uint32_t uq_grid(const eh_ctx* ctx, uint64_t items) {
+  const uint64_t g = (uint64_t)(ctx->cus > 0 ? ctx->cus : 1) * 32u;
+  return (uint32_t)(items < 1 ? 1 : items < g ? items : g);
+}
+// The digest pass (and, with `dedup`, the duplicate pass) over n cases of an arena: launches only, on `st`.  `pieces` bounds the
+// piece count (the kernels never write past it).
+static int uq_launch(eh_ctx* ctx, const uint8_t* d_data, const uint64_t* d_off, const uint64_t* d_len, const int32_t* d_status, uint64_t n, uint64_t pieces,
+                     bool digest, bool dedup, hipStream_t st) {
+  if (!n) return EH_OK;
+  uint64_t slots = 64; while (slots < 2 * n) slots <<= 1;
+  int rc = uq_ensure(ctx, n, pieces ? pieces : 1, slots); if (rc) return rc;
+  if (digest) {
+    hipLaunchKernelGGL(eh_uq_scan_kernel, dim3(1), dim3(64), 0, st, d_len, ctx->d_uq_pfirst, n);
+    hipLaunchKernelGGL(eh_uq_digest_kernel, dim3(uq_grid(ctx, pieces)), dim3(64), 0, st, d_data, d_off, d_len, (const uint64_t*)ctx->d_uq_pfirst, n, ctx->d_uq_term, pieces);
+    hipLaunchKernelGGL(eh_uq_combine_kernel, dim3(uq_grid(ctx, (n + 63) / 64)), dim3(64), 0, st, d_len, (const uint64_t*)ctx->d_uq_pfirst, n, (const unsigned long long*)ctx->d_uq_term, pieces,
+                       ctx->d_uq_digest);
+  }
+  if (dedup) {
+    unsigned long long* owner = ctx->d_uq_tab + 2; unsigned long long* rep = owner + slots;
+    const uint32_t gc = uq_grid(ctx, (n + 63) / 64);
+    hipLaunchKernelGGL(eh_uq_init_kernel, dim3(uq_grid(ctx, (2 + 2 * slots + 63) / 64)), dim3(64), 0, st, ctx->d_uq_tab, 2 + 2 * slots);
+    hipLaunchKernelGGL(eh_uq_insert_kernel, dim3(gc), dim3(64), 0, st, d_len, d_status, (const uint64_t*)ctx->d_uq_digest, n, owner, rep, slots, ctx->d_uq_first);
+    hipLaunchKernelGGL(eh_uq_resolve_kernel, dim3(gc), dim3(64), 0, st, (const unsigned long long*)rep, n, ctx->d_uq_first, ctx->d_uq_flag);
+    hipLaunchKernelGGL(eh_uq_compare_kernel, dim3(uq_grid(ctx, pieces)), dim3(64), 0, st, d_data, d_off, d_len, (const uint64_t*)ctx->d_uq_pfirst, n, (const uint64_t*)ctx->d_uq_first, ctx->d_uq_flag);
+    hipLaunchKernelGGL(eh_uq_final_kernel, dim3(gc), dim3(64), 0, st, d_len, d_status, n, ctx->d_uq_first, (const uint32_t*)ctx->d_uq_flag, ctx->d_uq_tab);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  return EH_OK;
+}
+// the last batch's digests / first_of in the context's device arrays (cached until the next batch)
+static int uq_result(eh_ctx* ctx, bool dedup) {
+  if (!ctx->have_result) { ctx->err = "no batch has run"; return EH_E_STATE; }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const uint64_t n = ctx->last_n;
+  const bool digest = ctx->uq_digest_seq != ctx->batch_seq;
+  dedup = dedup && ctx->uq_unique_seq != ctx->batch_seq;
+  if (!digest && !dedup) return EH_OK;
+  // every piece but a case's last is full: at most n + arena bytes / UQ_PIECE of them
+  const uint64_t arena = ctx->out_cap > ctx->out2_cap ? ctx->out_cap : ctx->out2_cap;
+  int rc = uq_launch(ctx, ctx->d_out, ctx->d_off, ctx->d_len, ctx->d_status, n, n + arena / UQ_PIECE + 1, digest, dedup, ctx->last_stream);
+  if (rc) return rc;
+  if (dedup) {
+    unsigned long long cnt[2] = {0, 0};
+    if (n) { HIPCHK(ctx, hipStreamSynchronize(ctx->last_stream)); HIPCHK(ctx, hipMemcpy(cnt, ctx->d_uq_tab, 16, hipMemcpyDeviceToHost)); }
+    ctx->uq_n_unique = cnt[0]; ctx->uq_bytes = cnt[1]; ctx->uq_unique_seq = ctx->batch_seq;
+  }
+  ctx->uq_digest_seq = ctx->batch_seq;
+  return EH_OK;
+}
+int eh_result_digests(eh_ctx* ctx, uint64_t* digest) {
+  if (!ctx) return EH_E_INVALID;
+  CO_GUARD(ctx);
+  int rc = uq_result(ctx, false); if (rc) return rc;
+  if (digest && ctx->last_n) { HIPCHK(ctx, hipStreamSynchronize(ctx->last_stream)); HIPCHK(ctx, hipMemcpy(digest, ctx->d_uq_digest, ctx->last_n * 8, hipMemcpyDeviceToHost)); }
+  return EH_OK;
+}
+int eh_result_unique(eh_ctx* ctx, uint64_t* first_of, uint64_t* n_unique, uint64_t* unique_bytes) {
+  if (!ctx) return EH_E_INVALID;
+  CO_GUARD(ctx);
+  int rc = uq_result(ctx, true); if (rc) return rc;
+  if (first_of && ctx->last_n) HIPCHK(ctx, hipMemcpy(first_of, ctx->d_uq_first, ctx->last_n * 8, hipMemcpyDeviceToHost));
+  if (n_unique) *n_unique = ctx->uq_n_unique;
+  if (unique_bytes) *unique_bytes = ctx->uq_bytes;
+  return EH_OK;
+}
+int eh_result_download_select(eh_ctx* ctx, const uint64_t* idx, uint64_t m, uint8_t* data, uint64_t cap, uint64_t* off) {
+  if (!ctx || (!idx && m)) return EH_E_INVALID;
+  CO_GUARD(ctx);
+  if (!ctx->have_result) { ctx->err = "no batch has run"; return EH_E_STATE; }
+  const uint64_t n = ctx->last_n;
+  for (uint64_t k = 0; k < m; k++) if (idx[k] >= n) { ctx->err = "eh_result_download_select: case index outside the last batch"; return EH_E_INVALID; }
+  int rc = eh_sync(ctx); if (rc) return rc;
+  std::vector<uint64_t> o(n ? n : 1), len(n ? n : 1);
+  if (n) { HIPCHK(ctx, hipMemcpy(o.data(), ctx->d_off, n * 8, hipMemcpyDeviceToHost)); HIPCHK(ctx, hipMemcpy(len.data(), ctx->d_len, n * 8, hipMemcpyDeviceToHost)); }
+  // the listed cases' offsets and lengths and where each goes, as the m-entry arrays the gather kernel reads: [0, m) offsets, [m, 2m) lengths, [2m, 3m] destinations
+  std::vector<uint64_t> sel(3 * m + 1), ord(m + 1);
+  uint64_t total = 0, maxlen = 0;
+  for (uint64_t k = 0; k < m; k++) { sel[k] = o[idx[k]]; sel[m + k] = len[idx[k]]; ord[k] = total; total += len[idx[k]]; if (len[idx[k]] > maxlen) maxlen = len[idx[k]]; }
+  ord[m] = total;
+  if (off) for (uint64_t k = 0; k <= m; k++) off[k] = ord[k];
+  if (!data || !total) return EH_OK;                                 // (no buffer: off says what is needed)
+  if (total > cap) { ctx->err = "eh_result_download_select: buffer too small"; return EH_E_INVALID; }
+  for (uint64_t k = 0; k <= m; k++) sel[2 * m + k] = ord[k];
+  if (ctx->sel_cap < 3 * m + 1) {
+    (void)hipFree(ctx->d_sel); ctx->d_sel = nullptr; ctx->sel_cap = 0;
+    HIPCHK(ctx, hipMalloc(&ctx->d_sel, (3 * m + 1) * 8));
+    ctx->sel_cap = 3 * m + 1;
+  }
+  HIPCHK(ctx, hipMemcpy(ctx->d_sel, sel.data(), (3 * m + 1) * 8, hipMemcpyHostToDevice));
+  return gather_download(ctx, data, m, ctx->d_sel, ctx->d_sel + m, ctx->d_sel + 2 * m, ord, maxlen);
+}
+// Self test hook: the same kernels over a caller-made arena (case i = data[off[i] .. off[i + 1]), status[i]); digest / first_of may be NULL.
+int eh_selftest_unique(eh_ctx* ctx, const uint8_t* data, const uint64_t* off, const int32_t* status, uint64_t n, uint64_t* digest, uint64_t* first_of) {
+  if (!ctx) return EH_E_INVALID;
+  if (!off || !status || (!data && off[n])) return EH_E_INVALID;
+  for (uint64_t i = 0; i < n; i++) if (off[i] > off[i + 1]) { ctx->err = "eh_selftest_unique: offsets must not decrease"; return EH_E_INVALID; }
+  CO_GUARD(ctx);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (ctx->have_result) { int rc = eh_sync(ctx); if (rc) return rc; }
+  ctx->uq_digest_seq = ctx->uq_unique_seq = 0;                       // the context's arrays are about to hold this arena's values
+  if (!n) return EH_OK;
+  const uint64_t nbytes = off[n] - off[0];
+  std::vector<uint64_t> len(n); uint64_t pieces = 0;
+  for (uint64_t i = 0; i < n; i++) { len[i] = off[i + 1] - off[i]; pieces += (len[i] + UQ_PIECE - 1) / UQ_PIECE; }
+  DevTmp dd, dof, dl, ds;
+  HIPCHK(ctx, hipMalloc(&dd.p, nbytes ? nbytes : 1)); HIPCHK(ctx, hipMalloc(&dof.p, n * 8)); HIPCHK(ctx, hipMalloc(&dl.p, n * 8)); HIPCHK(ctx, hipMalloc(&ds.p, n * 4));
+  if (nbytes) HIPCHK(ctx, hipMemcpy(dd.p, data + off[0], nbytes, hipMemcpyHostToDevice));
+  std::vector<uint64_t> rel(n); for (uint64_t i = 0; i < n; i++) rel[i] = off[i] - off[0];
+  HIPCHK(ctx, hipMemcpy(dof.p, rel.data(), n * 8, hipMemcpyHostToDevice));
+  HIPCHK(ctx, hipMemcpy(dl.p, len.data(), n * 8, hipMemcpyHostToDevice));
+  HIPCHK(ctx, hipMemcpy(ds.p, status, n * 4, hipMemcpyHostToDevice));
+  int rc = uq_launch(ctx, (const uint8_t*)dd.p, (const uint64_t*)dof.p, (const uint64_t*)dl.p, (const int32_t*)ds.p, n, pieces, true, first_of != nullptr, nullptr);
+  if (rc) return rc;
+  HIPCHK(ctx, hipStreamSynchronize(nullptr));
+  if (digest) HIPCHK(ctx, hipMemcpy(digest, ctx->d_uq_digest, n * 8, hipMemcpyDeviceToHost));
+  if (first_of) HIPCHK(ctx, hipMemcpy(first_of, ctx->d_uq_first, n * 8, hipMemcpyDeviceToHost));
   return EH_OK;
 }
 

@@ -21,6 +21,8 @@ EH_FLAG_SGML_NO_REPLAY = 16
 EH_FLAG_SGML_NO_LANES = 32
 EH_FLAG_NO_COOP = 64
 
+UNIQUE_PIECE_BYTES = 65536   # EH_UNIQUE_PIECE_BYTES: the uniqueness filter hands pieces of this size to the wavefronts
+
 CASE_OK, CASE_CRASHED, CASE_OVERFLOW, CASE_UNSUPPORTED, CASE_ARENA_FULL, CASE_BUDGET = 0, 1, 2, 3, 4, 5
 
 # every symbol include/erlamsa_hip.h declares
@@ -34,6 +36,7 @@ ABI_SYMBOLS = [
     "eh_corpus_device", "eh_stream", "eh_host_alloc", "eh_host_free", "eh_selftest_sort_by_priority", "eh_last_error_copy",
     "eh_comm_unique_id", "eh_comm_init", "eh_comm_init_local", "eh_comm_destroy", "eh_corpus_broadcast", "eh_corpus_allgather",
     "eh_corpus_broadcast_local", "eh_device_count", "eh_meta_atom_count", "eh_meta_atom_name", "eh_batch_done",
+    "eh_result_digests", "eh_result_unique", "eh_result_download_select", "eh_selftest_unique",
 ]
 
 
@@ -94,6 +97,10 @@ def load_library():
     lib.eh_result_prof.argtypes = [vp, vp]
     lib.eh_selftest_movers.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, vp]
     lib.eh_selftest_zlib.argtypes = [vp, C.c_int, vp, C.c_uint64, vp, C.c_uint64, vp, vp]
+    lib.eh_result_digests.argtypes = [vp, vp]
+    lib.eh_result_unique.argtypes = [vp, vp, u64p, u64p]
+    lib.eh_result_download_select.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp]
+    lib.eh_selftest_unique.argtypes = [vp, vp, vp, vp, C.c_uint64, vp, vp]
     lib.eh_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
     lib.eh_pool_stats.argtypes = [vp, vp]
     lib.eh_result_summary.argtypes = [vp, vp]
@@ -172,6 +179,7 @@ class Engine:
         self.h = h
         self._keep = []
         self.n_corpus = 0
+        self.last_n = 0
 
     def close(self):
         if self.h:
@@ -385,6 +393,52 @@ class Engine:
         buf = np.zeros(max(int(length), 1), dtype=np.uint8)
         self._chk(self.lib.eh_result_fetch(self.h, i, buf.ctypes.data, int(length), C.byref(ln)))
         return buf[:ln.value].tobytes()
+
+    # ---- uniqueness filter (eh_result_digests / eh_result_unique / eh_result_download_select)
+    def digests(self):
+        """uint64[n]: crc32c << 32 | crc32 of every case's output bytes, computed on the device (eh_result_digests)"""
+        n = self.last_n
+        d = np.zeros(max(n, 1), dtype=np.uint64)
+        self._chk(self.lib.eh_result_digests(self.h, d.ctypes.data))
+        return d[:n]
+
+    def unique(self):
+        """-> (first_of uint64[n], n_unique, unique_bytes): first_of[i] = the first EH_CASE_OK case with case i's bytes
+        (i itself for a case with another status) - eh_result_unique"""
+        n = self.last_n
+        f = np.zeros(max(n, 1), dtype=np.uint64)
+        nu, nb = C.c_uint64(), C.c_uint64()
+        self._chk(self.lib.eh_result_unique(self.h, f.ctypes.data, C.byref(nu), C.byref(nb)))
+        return f[:n], nu.value, nb.value
+
+    def download_select_into(self, idx, host_ptr, cap):
+        """outputs of the listed cases, in list order, into caller memory -> off uint64[m+1]; with host_ptr = None only the
+        offsets (off[m] = bytes needed)"""
+        idx = np.ascontiguousarray(idx, dtype=np.uint64)
+        off = np.zeros(len(idx) + 1, dtype=np.uint64)
+        self._chk(self.lib.eh_result_download_select(self.h, idx.ctypes.data, len(idx), C.c_void_p(host_ptr) if host_ptr else None, cap, off.ctypes.data))
+        return off
+
+    def download_select(self, idx):
+        """-> list[bytes]: the outputs of the listed cases of the last batch, in list order (eh_result_download_select)"""
+        idx = np.ascontiguousarray(idx, dtype=np.uint64)
+        total = int(self.download_select_into(idx, None, 0)[-1])
+        data = np.zeros(max(total, 1), dtype=np.uint8)
+        off = self.download_select_into(idx, data.ctypes.data, data.size)
+        buf = data.tobytes()
+        return [buf[int(off[k]):int(off[k + 1])] for k in range(len(idx))]
+
+    def selftest_unique(self, data, off, status, dedup=True):
+        """the filter's kernels over a caller-made arena (case i = data[off[i]:off[i+1]]) -> (digest uint64[n], first_of uint64[n] or None)"""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        status = np.ascontiguousarray(status, dtype=np.int32)
+        n = len(off) - 1
+        dig = np.zeros(max(n, 1), dtype=np.uint64)
+        first = np.zeros(max(n, 1), dtype=np.uint64) if dedup else None
+        self._chk(self.lib.eh_selftest_unique(self.h, data.ctypes.data, off.ctypes.data, status.ctypes.data, n, dig.ctypes.data,
+                                              first.ctypes.data if dedup else None))
+        return dig[:n], (first[:n] if dedup else None)
 
     def download_into(self, host_ptr, cap):
         """Case-ordered outputs of the last batch into caller memory at `host_ptr` (`cap` bytes; pinned or registered

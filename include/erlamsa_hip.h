@@ -290,6 +290,43 @@ int eh_meta_atom_count(void);
 const char* eh_meta_atom_name(int id);
 int eh_result_meta(eh_ctx* ctx, uint64_t i, uint8_t* buf, uint64_t cap, uint64_t* n_events);
 
+/* ---- uniqueness filter: per-case digests, duplicates found on the device, download of chosen cases (added within ABI 8; kernels in
+ * csrc/eh_unique.h).  Reference counterpart: none in erlamsa; radamsa, which it restates, has --hash / --checksums for the same
+ * purpose.  A batch repeats itself (one 44-byte request 4096 times under the default tables: 42 % of the outputs are repeats), and
+ * the device is the one place where dropping a repeat saves its trip over PCIe.
+ *
+ *   digest(i) = (uint64) crc32c(out_i) << 32 | crc32(out_i)      a function of the case's output bytes alone (not of its status)
+ *   crc32  = zlib's / erlang:crc32/1: reflected polynomial 0xEDB88320, init and final xor 0xFFFFFFFF, "123456789" -> 0xCBF43926
+ *   crc32c = the same construction with the reflected polynomial 0x82F63B78,                          "123456789" -> 0xE3069283
+ *   an empty output has digest 0.
+ *
+ * eh_result_digests  the digests of the last batch's n cases (digest may be NULL: computed and kept on the device only).
+ * eh_result_unique   first_of[i] = the smallest j <= i such that case j ended EH_CASE_OK and has the same bytes as case i; for a case
+ *                    with another status first_of[i] = i (it is not compared: the consumer routes it by its status).  *n_unique =
+ *                    EH_CASE_OK cases with first_of[i] == i, *unique_bytes = the sum of their lengths.  Empty EH_CASE_OK outputs are
+ *                    duplicates of the first of them.  Cases are grouped by (length, digest) and every member is then compared byte
+ *                    for byte with its group's first: no case is ever reported a duplicate of bytes that differ from its own.  The
+ *                    other way round there is one gap: when two DIFFERENT outputs share length and digest, the cases that differ
+ *                    from their group's first are reported unique (first_of[i] = i) even where they equal each other.  Such a pair
+ *                    can be constructed (both CRCs are affine), it is not a matter of chance: about 3e-8 for a batch of 2^20 cases.
+ * eh_result_download_select  the outputs of the m listed cases, in list order (any order, repeats allowed) and contiguous; off has
+ *                    m + 1 entries as in eh_result_download.  With or without EH_FLAG_ORDERED_OUTPUT; the same device gather and
+ *                    bounce buffers as eh_result_download.  EH_E_INVALID for an index >= n and when cap is too small - off[m] then
+ *                    says what is needed (data = NULL asks for the sizes only).
+ * All three: EH_E_STATE before a batch has run and on a context that has coalesced requests pending or in flight.  The results are
+ * kept per batch (a second call copies, it does not compute) and dropped by the next eh_fuzz_batch / eh_fuzz_calls.  A filter that
+ * persists across batches (radamsa's --checksums N) is the host's: the digests are what it would keep.
+ * EH_UNIQUE_PIECE_BYTES: both passes cut every case into pieces of this many bytes and hand the pieces, not the cases, to the
+ * wavefronts (a diagnostic constant: tests place cases around its multiples). */
+#define EH_UNIQUE_PIECE_BYTES 65536
+int eh_result_digests(eh_ctx* ctx, uint64_t* digest);
+int eh_result_unique(eh_ctx* ctx, uint64_t* first_of, uint64_t* n_unique, uint64_t* unique_bytes);
+int eh_result_download_select(eh_ctx* ctx, const uint64_t* idx, uint64_t m, uint8_t* data, uint64_t cap, uint64_t* off);
+/* Self test hook (tests only, like eh_selftest_movers): the same kernels over a caller-made arena.  off has n + 1 entries, case i is
+ * data[off[i] .. off[i+1]) with status[i]; digest and first_of (n entries each) may be NULL. */
+int eh_selftest_unique(eh_ctx* ctx, const uint8_t* data, const uint64_t* off, const int32_t* status, uint64_t n,
+                       uint64_t* digest, uint64_t* first_of);
+
 /* Per-case high-water mark of work memory in bytes (diagnostic; what sizes max_case_bytes and the pool's tiers). */
 int eh_result_peak(eh_ctx* ctx, uint64_t* peak);
 
