@@ -121,6 +121,44 @@ class EngineLimit(RuntimeError):
         self.cases, self.results = cases, results
 
 
+def fuzz_requests(requests, opts=None, return_status=False, device=0):
+    """N erlamsa_app:fuzz(Data, RequestOpts) calls in ONE launch: requests = [(data, request_opts)].  What erlamsa_esi reads from
+    every HTTP request (erlamsa_esi.erl:30-68) - seed, mutations, patterns, blockscale - comes from the request's own options and
+    falls back to `opts`; every other key (generators, ssrf_*, max_case_*, ...) comes from `opts`.  The requests' option sets become
+    option profiles of the engine (Engine.profile_add), their cases run side by side.
+    -> list with, per request, what fuzz/2 returns (the mutated binary, [] when the result is empty); with return_status the raw
+    outputs and the statuses, as fuzz_batch does.  A request that stopped at an engine limit raises EngineLimit unless
+    opts["on_engine_limit"] == "skip" or return_status is set."""
+    opts = dict(opts or {})
+    requests = [(bytes(d), dict(ro or {})) for d, ro in requests]
+    keys = host_only(opts)
+    for _, ro in requests:
+        keys += [k for k in host_only(ro) if k not in keys]
+    if keys:
+        raise Unsupported(keys)
+    eng = _engine(device)
+    _configure(eng, opts)
+    ids, seeds = [], []
+    for _, ro in requests:
+        per = {k: ro[k] if k in ro else opts.get(k) for k in ("seed", "mutations", "patterns", "blockscale")}
+        ids.append(eng.profile_add(actions_to_string(per["mutations"]), actions_to_string(per["patterns"]),
+                                   float(per["blockscale"] if per["blockscale"] is not None else 1.0)))
+        seeds.append(_seed_of(per))
+    data, off = pack_corpus([d for d, _ in requests])
+    eng.upload_corpus(data, off)
+    if not requests:
+        return ([], np.zeros(0, dtype=np.int32)) if return_status else []
+    eng.fuzz_calls(np.array(seeds, dtype=np.int64), np.array(ids, dtype=np.uint32))
+    outs, status = eng.download()
+    if return_status:
+        return outs, status
+    limited = [(i, int(s)) for i, s in enumerate(status) if s >= 2]
+    res = [o if s == CASE_OK and len(o) > 0 else [] for o, s in zip(outs, status)]
+    if limited and opts.get("on_engine_limit", "raise") != "skip":
+        raise EngineLimit(limited, res)
+    return res
+
+
 def fuzzer(opts):
     """erlamsa_main:fuzzer/1 for paths=[direct], output=return: the same input N times.
     Like record_result/2 (erlamsa_main.erl:120-122) empty results are dropped (a crashed worker, status 1, gives <<>>).

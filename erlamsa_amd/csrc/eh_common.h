@@ -126,6 +126,23 @@ struct DevConfig {
   char ssrf_port[12];
 };
 
+// ---- option profiles (eh_profile_add): what erlamsa_esi:parse_headers/2 reads from EVERY request besides the seed
+// (erlamsa_esi.erl:30-68) - mutations, patterns, blockscale - as the fields of DevConfig a case takes from its profile instead of from
+// the context's configuration.  Generators, the SSRF endpoint and every limit stay the context's (KParams::cfg).
+constexpr uint32_t MAX_PROFILES = 1024;   // EH_MAX_PROFILES
+struct ProfileCfg {
+  int32_t nsel;                      // as DevConfig, field by field
+  uint8_t sel_name[MAX_FS];
+  uint32_t sel_pri[MAX_FS];
+  int32_t npat;
+  int32_t pat_total;
+  uint8_t pat_id[P_COUNT];
+  uint8_t pad[2];
+  uint32_t pat_pri[P_COUNT];
+  uint32_t max_block_scaled;
+  uint32_t min_block_scaled;
+};
+
 // ---- cooperative execution of a heavy case's bulk loops (eh_device.h co_run / co_help) -------------------
 // A case runs on ONE wavefront.  Loops over hundreds of kilobytes - block copies, the final concatenation, the streaming
 // passes of eh_fuse2.h - are cut into chunks and posted on a board all contexts of the device share; wavefronts that are
@@ -201,6 +218,9 @@ struct KParams {
   uint32_t co_copy_min, co_copy_chunk;   // bytes: copies / compares of co_copy_min and more are posted in chunks of co_copy_chunk
   uint32_t co_fb_min, co_fb_chunk;       // positions: the same for the streaming passes of eh_fuse2.h (chunk: a multiple of 1024)
   uint32_t co_linger, pad_co;            // wavefronts of a pass that stay for posted chunks once the pass is out of tickets
+  // mode 1 with option profiles (eh_fuzz_calls_profiled): case i runs under profiles[profile_id[i]].  Both nullptr otherwise.
+  const EH_G ProfileCfg* profiles;
+  const EH_G uint32_t* profile_id;       // n
 };
 
 struct MutaInfo { const char* name; int pri; int on_gpu; };

@@ -312,6 +312,7 @@ struct Ctx {
   int nb, cur;
   EH_G Blk* em;
   int nem;
+  uint32_t max_block_scaled;   // round(MAX_BLOCK_SIZE * blockscale) of the case's configuration: the context's, or its option profile's
   bptr aux;        // per-slot mutator state (lis/lrs lines, fo block)
   // linear work allocator
   bptr ws;
@@ -333,6 +334,7 @@ struct Ctx {
   uint64_t call_bin; uint32_t call_len;
   EH_G MuFrame* mu;
   uint64_t t_case;     // cycle stamp at which the case began (mux_fuzzers raises the wavefront's issue priority for cases that run long)
+  uint32_t min_block_scaled;   // round(MIN_BLOCK_SIZE * blockscale), likewise (the two sit where the struct had padding: the LDS footprint is unchanged)
   int32_t m_aux;       // set by the mutators whose own Meta entry does not follow from their result alone (num: a number found; ab / ad: stringy)
   uint64_t ws_peak, ws_top;   // diagnostics: highest ws_used, bytes taken from the top of chunks (eh_result_peak)
   int status;

@@ -21,6 +21,7 @@
 #include <map>
 #include <mutex>
 #include <thread>
+#include <unordered_map>
 #include <string>
 #include <vector>
 
@@ -68,7 +69,11 @@ EH_DEV int run_mutator_ext(Ctx& c, uint32_t fn, uint32_t mask) {
 // =============================================================================================
 // device: per-run setup  (erlamsa_main.erl:134-158)
 // =============================================================================================
-EH_DEV void setup_run(const DevConfig& cfg, int64_t s1, int64_t s2, int64_t s3, Rng& rng, int& gen, int& snand_mask,
+// `sel` holds the selected mutators (nsel, sel_name, sel_pri): the context's DevConfig or, for a case of a profiled launch, its
+// ProfileCfg; `cfg` holds the generators.  Both are template parameters so that each keeps the address space it is passed with
+// (kernel argument or global memory): one generic reference for the two would turn the table loads into flat_* instructions.
+template <class Sel, class Gen>
+EH_DEV void setup_run(const Sel& sel, const Gen& cfg, int64_t s1, int64_t s2, int64_t s3, Rng& rng, int& gen, int& snand_mask,
                       uint32_t& e_pri, uint32_t& e_meta, int& nfs) {
   const int l = EH_LANE;
   rng.draws = 0;
@@ -78,7 +83,7 @@ EH_DEV void setup_run(const DevConfig& cfg, int64_t s1, int64_t s2, int64_t s3, 
   (void)rng_rand(rng, 1);                                      // :1314
   // make_mutator (:1370-1383): Mutas = selected entries in REVERSE table order;
   // mutators_mutator (:1391-1395) draws rand(10) along that list and prepends => list in table order.
-  nfs = cfg.nsel;
+  nfs = sel.nsel;
   uint32_t score = 0;
   if (l < nfs) {
     double u = rng_peek(rng, (uint32_t)(nfs - 1 - l) + 1);
@@ -86,8 +91,8 @@ EH_DEV void setup_run(const DevConfig& cfg, int64_t s1, int64_t s2, int64_t s3, 
     score = n < 2 ? 2 : n;
   }
   rng_skip(rng, (uint64_t)nfs);
-  uint32_t name = l < nfs ? cfg.sel_name[l] : 0;
-  e_pri = l < nfs ? cfg.sel_pri[l] : 0;
+  uint32_t name = l < nfs ? sel.sel_name[l] : 0;
+  e_pri = l < nfs ? sel.sel_pri[l] : 0;
   uint32_t mask = name == M_SNAND ? (uint32_t)snand_mask : 3u;
   e_meta = em_pack(score, name, name, mask);
   // mux_generators (erlamsa_gen.erl:194-199): rand(N) over the priority-sorted list
@@ -97,6 +102,18 @@ EH_DEV void setup_run(const DevConfig& cfg, int64_t s1, int64_t s2, int64_t s3, 
     if (g == 0 || g < cfg.gen_pri[i]) { gen = cfg.gen_id[i]; break; }
     g -= cfg.gen_pri[i];
   }
+}
+struct SelView { int32_t nsel; const EH_G uint8_t* sel_name; const EH_G uint32_t* sel_pri; };   // the `sel` of a mode-1 case: the context's tables or its profile's, global memory either way
+// choose_pattern_fun (erlamsa_patterns.erl:431-434) + choose_pri over the priority-sorted patterns of `t` (DevConfig or ProfileCfg); -1: none
+template <class Pats>
+EH_DEV int choose_pattern(const Pats& t, Rng& rng) {
+  uint32_t r = rng_rand(rng, (uint32_t)t.pat_total);
+  int pat = t.npat > 0 ? t.pat_id[t.npat - 1] : -1;
+  for (int k = 0; k < t.npat; k++) {
+    if (r == 0 || r < t.pat_pri[k]) { pat = t.pat_id[k]; break; }
+    r -= t.pat_pri[k];
+  }
+  return pat;
 }
 
 // One wavefront in front of every eh_mutate_kernel: the batch's counters back to zero, its argument block written to device memory,
@@ -121,7 +138,7 @@ __global__ void __launch_bounds__(64) eh_prologue_kernel(KParams p, int64_t s1, 
   for (int i = l; i < (int)(sizeof(KParams) / 4); i += 64) dst[i] = src[i];
   if (p.mode != 0) return;
   Rng rng; int gen, mask, nfs; uint32_t e_pri, e_meta;
-  setup_run(p.cfg, s1, s2, s3, rng, gen, mask, e_pri, e_meta, nfs);
+  setup_run(p.cfg, p.cfg, s1, s2, s3, rng, gen, mask, e_pri, e_meta, nfs);
   if (l == 0) { out->a1 = rng.a1; out->a2 = rng.a2; out->a3 = rng.a3; out->gen = gen; out->nfs = nfs; out->snand_mask = mask; }
   if (l < nfs) { out->fs_name[l] = (uint8_t)em_name(e_meta); out->fs_score[l] = (uint8_t)em_score(e_meta); out->fs_pri[l] = e_pri; }
 }
@@ -755,9 +772,8 @@ EH_DEV void gen_finish(Ctx& c, uint32_t len) {
   }
 }
 EH_DEV uint32_t rand_block_size(Ctx& c) {                              // :55-56
-  const DevConfig& cfg = c.p->cfg;
-  uint32_t r = rng_rand(c.rng, cfg.max_block_scaled);
-  return r > cfg.min_block_scaled ? r : cfg.min_block_scaled;
+  uint32_t r = rng_rand(c.rng, c.max_block_scaled);
+  return r > c.min_block_scaled ? r : c.min_block_scaled;
 }
 EH_DEV void gen_direct(Ctx& c, cbptr in, uint32_t L) {       // erlamsa_gen.erl:152-164 (split_binary guard never holds)
   (void)rand_block_size(c);
@@ -815,10 +831,9 @@ __device__ __noinline__ void gen_force(Ctx&) {
   wave_sync();
 }
 EH_DEV void gen_random(Ctx& c) {                                       // random_stream/1 :167-178
-  const DevConfig& cfg = c.p->cfg;
   c.nb = 0;
   while (c.status == CASE_OK) {
-    uint32_t n = rng_range(c.rng, 32, cfg.max_block_scaled);
+    uint32_t n = rng_range(c.rng, 32, c.max_block_scaled);
     bptr dst = ws_alloc_grow(c, n);
     if (!dst) return;
     random_block_rev(c, dst, n);
@@ -959,6 +974,7 @@ __global__ void __launch_bounds__(64, EH_WAVES_PER_SIMD) eh_mutate_kernel(const 
     wave_sync();
     int gen;
     Rng pr;
+    c.max_block_scaled = p.cfg.max_block_scaled; c.min_block_scaled = p.cfg.min_block_scaled;
     if (p.mode == 0) {
       // ThreadSeed of case I = parent draws 3(I-1)+1..3(I-1)+3   (erlamsa_main.erl:179, erlamsa_rnd.erl:65)
       pr = parent;
@@ -966,7 +982,13 @@ __global__ void __launch_bounds__(64, EH_WAVES_PER_SIMD) eh_mutate_kernel(const 
       gen = gen0; lt.e_pri = pri0; lt.e_meta = meta0; c.nfs = nfs0;
     } else {
       int mask;
-      setup_run(p.cfg, p.seeds[3 * i], p.seeds[3 * i + 1], p.seeds[3 * i + 2], pr, gen, mask, lt.e_pri, lt.e_meta, c.nfs);
+      SelView sel = {p.cfg.nsel, p.cfg.sel_name, p.cfg.sel_pri};
+      if (p.profile_id) {
+        const EH_G ProfileCfg* pf = p.profiles + uni(p.profile_id[i]);     // the case's option profile, wave-uniform (the host has checked every id against the table's size)
+        c.max_block_scaled = uni(pf->max_block_scaled); c.min_block_scaled = uni(pf->min_block_scaled);
+        sel.nsel = (int32_t)uni((uint32_t)pf->nsel); sel.sel_name = pf->sel_name; sel.sel_pri = pf->sel_pri;
+      }
+      setup_run(sel, p.cfg, p.seeds[3 * i], p.seeds[3 * i + 1], p.seeds[3 * i + 2], pr, gen, mask, lt.e_pri, lt.e_meta, c.nfs);
     }
 #ifdef EH_PROF
 #define EH_PH(k) do { uint64_t now_ = __builtin_readcyclecounter(); if (l == 0) { atomicAdd(&p.prof[2 * (64 + (k))], (unsigned long long)(now_ - ph0)); atomicAdd(&p.prof[2 * (64 + (k)) + 1], 1ull); } ph0 = now_; } while (0)
@@ -990,12 +1012,7 @@ __global__ void __launch_bounds__(64, EH_WAVES_PER_SIMD) eh_mutate_kernel(const 
 
     if (c.status == CASE_OK) {
       // choose_pattern_fun (erlamsa_patterns.erl:431-434) + choose_pri
-      uint32_t r = rng_rand(c.rng, (uint32_t)p.cfg.pat_total);
-      int pat = p.cfg.npat > 0 ? p.cfg.pat_id[p.cfg.npat - 1] : -1;
-      for (int k = 0; k < p.cfg.npat; k++) {
-        if (r == 0 || r < p.cfg.pat_pri[k]) { pat = p.cfg.pat_id[k]; break; }
-        r -= p.cfg.pat_pri[k];
-      }
+      const int pat = p.mode != 0 && p.profile_id ? choose_pattern(p.profiles[uni(p.profile_id[i])], c.rng) : choose_pattern(p.cfg, c.rng);
       if (pat < 0) c.status = CASE_CRASHED; else run_patterns(c, lt, pat);  // Pat(Ll, CurMuta, Meta) :189
     }
 
@@ -1206,14 +1223,19 @@ struct eh_ctx {
   unsigned long long* d_counters = nullptr;  // [0] ticket, [1] out cursor, [2] input bytes, [3] cases done, [4] lingering wavefronts, [5] output bytes, [6] workgroups that left, [8, 264) EH_PROF, [264, 270) cases by status
   unsigned long long* h_sum = nullptr; uint64_t batch_seq = 0;   // page-locked: the last batch's totals, written by the kernel (KParams::summary_out)
   RunState* d_run = nullptr;
-  int64_t* d_seeds = nullptr; uint64_t seeds_cap = 0;
+  int64_t* d_seeds = nullptr; uint64_t seeds_cap = 0;  // mode 1: 3 x seeds_cap seeds, then seeds_cap profile ids (uint32) in the same allocation
+  // option profiles (eh_profile_add), guarded by co_lock.  profiles[0] = what eh_configure was given; entries are never changed once made,
+  // ids only grow until the next eh_configure.  The device table has room for all EH_MAX_PROFILES; entries [0, profiles_on_device) of it
+  // are current, the rest is copied before the next profiled launch (launches of one context run one after the other).
+  std::vector<ProfileCfg> profiles; std::unordered_map<std::string, uint32_t> profile_index;
+  ProfileCfg* d_profiles = nullptr; uint32_t profiles_on_device = 0;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   // request coalescing (eh_submit / eh_flush / eh_poll)
   std::recursive_mutex co_lock;
   std::condition_variable_any co_cv; bool co_collecting = false;   // a thread is waiting for / downloading the in-flight batch (lock released)
   bool co_internal = false;                             // co_launch / co_collect are calling the batch entry points themselves
   uint64_t co_next_ticket = 1, co_flush_cases = 4096, co_flush_bytes = 64ull << 20;
-  std::vector<uint8_t> co_data; std::vector<uint64_t> co_off{0}; std::vector<int64_t> co_seeds; std::vector<uint64_t> co_tickets;   // pending batch
+  std::vector<uint8_t> co_data; std::vector<uint64_t> co_off{0}; std::vector<int64_t> co_seeds; std::vector<uint32_t> co_profile; std::vector<uint64_t> co_tickets;   // pending batch
   bool co_inflight = false; std::vector<uint64_t> co_inflight_tickets;                  // launched, results still on the device
   struct CoResult { std::vector<uint8_t> out; int32_t status; };
   std::vector<uint64_t> co_cancelled;                                                   // in-flight tickets nobody will poll
@@ -1285,6 +1307,50 @@ static int parse_actions(eh_ctx* ctx, const char* s, bool muta, std::vector<long
   }
   return EH_OK;
 }
+
+// The part of the option map a PROFILE owns - mutations, patterns, blockscale - parsed as erlamsa_main:fuzzer/1 reads them
+// (erlamsa_main.erl:127-163).  eh_configure and eh_profile_add both come through here, so a profile is the context's configuration
+// bit for bit when the strings are the same.  `pc` is written only on success and has no uninitialised byte (profiles are interned
+// by their bytes).
+static int parse_profile(eh_ctx* ctx, const char* mutations, const char* patterns, double blockscale, ProfileCfg& pc) {
+  ProfileCfg cfg;
+  memset(&cfg, 0, sizeof(cfg));
+  std::vector<long> mp, pp;
+  int rc = parse_actions(ctx, mutations, true, mp); if (rc) return rc;
+  rc = parse_actions(ctx, patterns, false, pp); if (rc) return rc;
+  for (int i = 0; i < M_COUNT; i++) if (mp[i] >= 0) {
+    if (!MUTAS[i].on_gpu) { ctx->err = std::string("mutator '") + MUTAS[i].name + "' is not available on the GPU in this build"; return EH_E_UNSUPPORTED; }
+    cfg.sel_name[cfg.nsel] = (uint8_t)i; cfg.sel_pri[cfg.nsel] = (uint32_t)mp[i]; cfg.nsel++;
+  }
+  // make_pattern (erlamsa_patterns.erl:416-428): foldl prepends => reversed table order, then sort_by_priority
+  PL pl;
+  for (int i = P_COUNT - 1; i >= 0; i--) if (pp[i] >= 0) {
+    if (!PATS[i].on_gpu) { ctx->err = std::string("pattern '") + PATS[i].name + "' is not available on the GPU in this build"; return EH_E_UNSUPPORTED; }
+    pl.push_back({(uint32_t)pp[i], i});
+  }
+  PL sp = otp_sort_desc_strict(pl);
+  cfg.npat = (int)sp.size();
+  for (size_t i = 0; i < sp.size(); i++) { cfg.pat_id[i] = (uint8_t)sp[i].id; cfg.pat_pri[i] = sp[i].pri; cfg.pat_total += (int)sp[i].pri; }
+  if (cfg.npat == 0) { ctx->err = "no patterns selected"; return EH_E_INVALID; }
+  double bs = blockscale == 0 ? 1.0 : blockscale;
+  cfg.max_block_scaled = (uint32_t)llround(MAX_BLOCK_SIZE * bs);
+  cfg.min_block_scaled = (uint32_t)llround(MIN_BLOCK_SIZE * bs);
+  pc = cfg;
+  return EH_OK;
+}
+static std::string profile_key(const ProfileCfg& pc) { return std::string((const char*)&pc, sizeof(pc)); }
+
+// Device memory of a mode-1 launch of up to n cases: the seeds and, behind them, the cases' profile ids; and the profile table.
+static int ensure_seeds(eh_ctx* ctx, uint64_t n) {
+  if (!ctx->d_profiles) HIPCHK(ctx, hipMalloc(&ctx->d_profiles, MAX_PROFILES * sizeof(ProfileCfg)));
+  if (n <= ctx->seeds_cap) return EH_OK;
+  if (ctx->d_seeds) (void)hipFree(ctx->d_seeds);
+  ctx->d_seeds = nullptr; ctx->seeds_cap = 0;
+  HIPCHK(ctx, hipMalloc(&ctx->d_seeds, n * 24 + n * 4));
+  ctx->seeds_cap = n;
+  return EH_OK;
+}
+static uint32_t* profile_ids_of(eh_ctx* ctx) { return (uint32_t*)(ctx->d_seeds + 3 * ctx->seeds_cap); }
 
 static int ensure_results(eh_ctx* ctx, uint64_t n) {
   if (n <= ctx->res_cap) return EH_OK;
@@ -1434,7 +1500,7 @@ static int reserve(eh_ctx* ctx, uint64_t n, uint64_t in_bytes) {
   return EH_OK;
 }
 
-static int launch(eh_ctx* ctx, int mode, const int64_t seed[3], uint64_t first_case, uint64_t corpus_first, uint64_t n, hipStream_t st) {
+static int launch(eh_ctx* ctx, int mode, const int64_t seed[3], uint64_t first_case, uint64_t corpus_first, uint64_t n, hipStream_t st, bool profiled = false) {
   if (!ctx->configured || !ctx->d_corpus) { ctx->err = "configure and load a corpus first"; return EH_E_STATE; }
   if (corpus_first + n > ctx->n_corpus || (mode == 0 && first_case < 1)) { ctx->err = "case range outside the corpus"; return EH_E_INVALID; }
   // make_generator_fun (erlamsa_gen.erl:215-224) drops `file` without paths and `jump` with fewer than two: said aloud here
@@ -1451,6 +1517,7 @@ static int launch(eh_ctx* ctx, int mode, const int64_t seed[3], uint64_t first_c
   memset(&p, 0, sizeof(p));
   p.corpus = dp(ctx->d_corpus); p.coff = dp(ctx->d_coff); p.corpus_first = corpus_first; p.n_paths = ctx->n_corpus; p.n = n; p.first_case = first_case;
   p.mode = mode; p.run = dp(ctx->d_run); p.seeds = dp(ctx->d_seeds); p.cfg = ctx->cfg;
+  if (profiled) { p.profiles = dp(ctx->d_profiles); p.profile_id = dp(profile_ids_of(ctx)); }   // (memset above: nullptr otherwise)
   const DevPool* pl = ctx->pool;
   p.work_cap = pl->work_cap;
   p.work_budget = ctx->work_budget;                                            // 0 = no budget (the default)
@@ -1597,7 +1664,7 @@ void eh_destroy(eh_ctx* ctx) {
   pool_release(ctx);
   (void)hipFree(ctx->d_slots); (void)hipFree(ctx->d_out); (void)hipFree(ctx->d_off); (void)hipFree(ctx->d_len);
   (void)hipFree(ctx->d_status); (void)hipFree(ctx->d_draws); (void)hipFree(ctx->d_lastm); (void)hipFree(ctx->d_cycles); (void)hipFree(ctx->d_peak); (void)hipFree(ctx->d_toff); (void)hipFree(ctx->d_tlen); (void)hipFree(ctx->d_counters); if (ctx->h_sum) (void)hipHostFree(ctx->h_sum);
-  (void)hipFree(ctx->d_run); (void)hipFree(ctx->d_seeds);
+  (void)hipFree(ctx->d_run); (void)hipFree(ctx->d_seeds); (void)hipFree(ctx->d_profiles);
   for (int k = 0; k < 2; k++) { if (ctx->d_bounce[k]) (void)hipFree(ctx->d_bounce[k]); if (ctx->ev_g[k]) (void)hipEventDestroy(ctx->ev_g[k]); if (ctx->ev_c[k]) (void)hipEventDestroy(ctx->ev_c[k]); }
   if (ctx->dl_gather) (void)hipStreamDestroy(ctx->dl_gather);
   if (ctx->dl_copy) (void)hipStreamDestroy(ctx->dl_copy);
@@ -1631,23 +1698,11 @@ int eh_configure(eh_ctx* ctx, const eh_options* o) {
   }
   DevConfig cfg;
   memset(&cfg, 0, sizeof(cfg));
-  std::vector<long> mp, pp;
-  int rc = parse_actions(ctx, o->mutations, true, mp); if (rc) return rc;
-  rc = parse_actions(ctx, o->patterns, false, pp); if (rc) return rc;
-  for (int i = 0; i < M_COUNT; i++) if (mp[i] >= 0) {
-    if (!MUTAS[i].on_gpu) { ctx->err = std::string("mutator '") + MUTAS[i].name + "' is not available on the GPU in this build"; return EH_E_UNSUPPORTED; }
-    cfg.sel_name[cfg.nsel] = (uint8_t)i; cfg.sel_pri[cfg.nsel] = (uint32_t)mp[i]; cfg.nsel++;
-  }
-  // make_pattern (erlamsa_patterns.erl:416-428): foldl prepends => reversed table order, then sort_by_priority
-  PL pl;
-  for (int i = P_COUNT - 1; i >= 0; i--) if (pp[i] >= 0) {
-    if (!PATS[i].on_gpu) { ctx->err = std::string("pattern '") + PATS[i].name + "' is not available on the GPU in this build"; return EH_E_UNSUPPORTED; }
-    pl.push_back({(uint32_t)pp[i], i});
-  }
-  PL sp = otp_sort_desc_strict(pl);
-  cfg.npat = (int)sp.size();
-  for (size_t i = 0; i < sp.size(); i++) { cfg.pat_id[i] = (uint8_t)sp[i].id; cfg.pat_pri[i] = sp[i].pri; cfg.pat_total += (int)sp[i].pri; }
-  if (cfg.npat == 0) { ctx->err = "no patterns selected"; return EH_E_INVALID; }
+  ProfileCfg p0;
+  int rc = parse_profile(ctx, o->mutations, o->patterns, o->blockscale, p0); if (rc) return rc;
+  cfg.nsel = p0.nsel; memcpy(cfg.sel_name, p0.sel_name, sizeof(cfg.sel_name)); memcpy(cfg.sel_pri, p0.sel_pri, sizeof(cfg.sel_pri));
+  cfg.npat = p0.npat; cfg.pat_total = p0.pat_total; memcpy(cfg.pat_id, p0.pat_id, sizeof(cfg.pat_id)); memcpy(cfg.pat_pri, p0.pat_pri, sizeof(cfg.pat_pri));
+  cfg.max_block_scaled = p0.max_block_scaled; cfg.min_block_scaled = p0.min_block_scaled;
   // generators: table order of erlamsa_gen:generators/0 is random(1) ... direct(500)
   long gr = 1, gd = 500, gf = -1, gj = -1;
   if (o->generators) {
@@ -1675,11 +1730,14 @@ int eh_configure(eh_ctx* ctx, const eh_options* o) {
   PL sg = otp_sort_desc_strict(gl);
   cfg.ngen = (int)sg.size();
   for (size_t i = 0; i < sg.size(); i++) { cfg.gen_id[i] = (uint8_t)sg[i].id; cfg.gen_pri[i] = sg[i].pri; cfg.gen_total += (int)sg[i].pri; }
-  double bs = o->blockscale == 0 ? 1.0 : o->blockscale;
-  cfg.max_block_scaled = (uint32_t)llround(MAX_BLOCK_SIZE * bs);
-  cfg.min_block_scaled = (uint32_t)llround(MIN_BLOCK_SIZE * bs);
   snprintf(cfg.ssrf_host, sizeof(cfg.ssrf_host), "%s", o->ssrf_host ? o->ssrf_host : "localhost");
   snprintf(cfg.ssrf_port, sizeof(cfg.ssrf_port), "%d", o->ssrf_port ? o->ssrf_port : 51234);
+  // all profiles go, their ids with them; profile 0 is this configuration
+  try {
+    std::vector<ProfileCfg> one(1, p0); std::unordered_map<std::string, uint32_t> idx; idx.emplace(profile_key(p0), 0u);
+    ctx->profiles.swap(one); ctx->profile_index.swap(idx);
+  } catch (const std::bad_alloc&) { ctx->err = "out of host memory"; return EH_E_NOMEM; }
+  ctx->profiles_on_device = 0;
   ctx->cfg = cfg;
   ctx->work_budget = o->max_case_work;
   ctx->big_case_bytes = o->big_case_bytes; ctx->max_case_bytes = o->max_case_bytes; ctx->out_capacity_opt = o->out_capacity; ctx->max_slots_opt = o->max_slots; ctx->flags = o->flags;
@@ -1918,7 +1976,9 @@ int eh_corpus_broadcast_local(eh_ctx** ctxs, int nctx, int root) {
 int eh_reserve(eh_ctx* ctx, uint64_t max_cases) {
   if (!ctx) return EH_E_INVALID;
   if (!ctx->configured || !ctx->d_corpus) { ctx->err = "configure and load a corpus first"; return EH_E_STATE; }
-  return reserve(ctx, max_cases, 0);
+  std::lock_guard<std::recursive_mutex> g(ctx->co_lock);
+  int rc = reserve(ctx, max_cases, 0);
+  return rc ? rc : ensure_seeds(ctx, max_cases);     // (per-call seeds and profile ids: eh_fuzz_calls / eh_fuzz_calls_profiled never allocate either)
 }
 
 int eh_fuzz_batch(eh_ctx* ctx, const int64_t seed[3], uint64_t first_case, uint64_t corpus_first, uint64_t n, void* stream) {
@@ -1926,20 +1986,62 @@ int eh_fuzz_batch(eh_ctx* ctx, const int64_t seed[3], uint64_t first_case, uint6
   CO_GUARD(ctx);
   return launch(ctx, 0, seed, first_case, corpus_first, n, (hipStream_t)stream);
 }
-int eh_fuzz_calls(eh_ctx* ctx, const int64_t* seeds, uint64_t corpus_first, uint64_t n, void* stream) {
+static int fuzz_calls(eh_ctx* ctx, const int64_t* seeds, const uint32_t* profile, uint64_t corpus_first, uint64_t n, void* stream) {
   if (!ctx || !seeds) return EH_E_INVALID;
   CO_GUARD(ctx);
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (n > ctx->seeds_cap) {
-    if (ctx->d_seeds) (void)hipFree(ctx->d_seeds);
-    ctx->d_seeds = nullptr;
-    HIPCHK(ctx, hipMalloc(&ctx->d_seeds, n * 24));
-    ctx->seeds_cap = n;
+  if (profile) {
+    if (!ctx->configured) { ctx->err = "configure first"; return EH_E_STATE; }
+    const uint32_t count = (uint32_t)ctx->profiles.size();
+    for (uint64_t i = 0; i < n; i++) if (profile[i] >= count) { ctx->err = "case " + std::to_string(i) + ": no profile " + std::to_string(profile[i]) + " (eh_profile_count = " + std::to_string(count) + ")"; return EH_E_INVALID; }
   }
-  // synchronous copy: the caller's `seeds` may be freed or reused as soon as this call returns
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  int rc = ensure_seeds(ctx, n);
+  if (rc) return rc;
+  // synchronous copies: the caller's arrays may be freed or reused as soon as this call returns
   if (n) { HIPCHK(ctx, hipStreamSynchronize((hipStream_t)stream)); HIPCHK(ctx, hipMemcpy(ctx->d_seeds, seeds, n * 24, hipMemcpyHostToDevice)); }
+  if (profile && n) {
+    HIPCHK(ctx, hipMemcpy(profile_ids_of(ctx), profile, n * 4, hipMemcpyHostToDevice));
+    // profiles added since the last profiled launch.  The context's previous batch on this stream has ended (the wait above), and
+    // entries below profiles_on_device are never rewritten: no kernel reads what is copied here.
+    const uint32_t have = ctx->profiles_on_device, count = (uint32_t)ctx->profiles.size();
+    if (count > have) HIPCHK(ctx, hipMemcpy(ctx->d_profiles + have, ctx->profiles.data() + have, (size_t)(count - have) * sizeof(ProfileCfg), hipMemcpyHostToDevice));
+    ctx->profiles_on_device = count;
+  }
   int64_t dummy[3] = {0, 0, 0};
-  return launch(ctx, 1, dummy, 1, corpus_first, n, (hipStream_t)stream);
+  return launch(ctx, 1, dummy, 1, corpus_first, n, (hipStream_t)stream, profile != nullptr && n > 0);
+}
+int eh_fuzz_calls(eh_ctx* ctx, const int64_t* seeds, uint64_t corpus_first, uint64_t n, void* stream) {
+  return fuzz_calls(ctx, seeds, nullptr, corpus_first, n, stream);
+}
+int eh_fuzz_calls_profiled(eh_ctx* ctx, const int64_t* seeds, const uint32_t* profile, uint64_t corpus_first, uint64_t n, void* stream) {
+  if (!profile) return EH_E_INVALID;
+  return fuzz_calls(ctx, seeds, profile, corpus_first, n, stream);
+}
+// ---- option profiles ----------------------------------------------------------------------------------------
+int eh_profile_add(eh_ctx* ctx, const char* mutations, const char* patterns, double blockscale, uint32_t* id) {
+  if (!ctx || !id) return EH_E_INVALID;
+  std::lock_guard<std::recursive_mutex> g(ctx->co_lock);
+  if (!ctx->configured) { ctx->err = "configure first"; return EH_E_STATE; }
+  ProfileCfg pc;
+  int rc = parse_profile(ctx, mutations, patterns, blockscale, pc);
+  if (rc) return rc;
+  try {
+    const std::string key = profile_key(pc);
+    auto it = ctx->profile_index.find(key);
+    if (it != ctx->profile_index.end()) { *id = it->second; return EH_OK; }
+    if (ctx->profiles.size() >= MAX_PROFILES) { ctx->err = "the profile table is full (EH_MAX_PROFILES = " + std::to_string(MAX_PROFILES) + "): eh_configure starts a new one"; return EH_E_NOMEM; }
+    ctx->profiles.reserve(ctx->profiles.size() + 1);
+    ctx->profile_index.emplace(key, (uint32_t)ctx->profiles.size());
+    ctx->profiles.push_back(pc);                          // (room reserved above: cannot throw)
+  } catch (const std::bad_alloc&) { ctx->err = "out of host memory"; return EH_E_NOMEM; }
+  *id = (uint32_t)ctx->profiles.size() - 1;
+  return EH_OK;
+}
+int eh_profile_count(eh_ctx* ctx, uint32_t* n) {
+  if (!ctx || !n) return EH_E_INVALID;
+  std::lock_guard<std::recursive_mutex> g(ctx->co_lock);
+  *n = (uint32_t)ctx->profiles.size();
+  return EH_OK;
 }
 // ---- request coalescing -------------------------------------------------------------------------------------
 // Brings the launched batch's results to the host (one download) and files them under their tickets.
@@ -1982,11 +2084,13 @@ static int co_launch(eh_ctx* ctx) {
   const uint64_t n = ctx->co_tickets.size();
   ctx->co_internal = true;
   rc = eh_corpus_upload(ctx, ctx->co_data.data(), ctx->co_off.data(), n);
-  if (!rc) rc = eh_fuzz_calls(ctx, ctx->co_seeds.data(), 0, n, nullptr);
+  bool profiled = false;                                            // requests that all run under profile 0 take the unprofiled launch
+  for (uint32_t id : ctx->co_profile) profiled = profiled || id != 0;
+  if (!rc) rc = fuzz_calls(ctx, ctx->co_seeds.data(), profiled ? ctx->co_profile.data() : nullptr, 0, n, nullptr);
   ctx->co_internal = false;
   if (rc) return rc;
   ctx->co_inflight = true; ctx->co_inflight_tickets.swap(ctx->co_tickets);
-  ctx->co_tickets.clear(); ctx->co_data.clear(); ctx->co_off.assign(1, 0); ctx->co_seeds.clear();
+  ctx->co_tickets.clear(); ctx->co_data.clear(); ctx->co_off.assign(1, 0); ctx->co_seeds.clear(); ctx->co_profile.clear();
   return EH_OK;
 }
 int eh_coalesce_limits(eh_ctx* ctx, uint64_t flush_cases, uint64_t flush_bytes) {
@@ -1996,17 +2100,22 @@ int eh_coalesce_limits(eh_ctx* ctx, uint64_t flush_cases, uint64_t flush_bytes) 
   return EH_OK;
 }
 int eh_submit(eh_ctx* ctx, const uint8_t* data, uint64_t len, const int64_t seed[3], uint64_t* ticket) {
+  return eh_submit_profiled(ctx, data, len, seed, 0, ticket);
+}
+int eh_submit_profiled(eh_ctx* ctx, const uint8_t* data, uint64_t len, const int64_t seed[3], uint32_t profile, uint64_t* ticket) {
   if (!ctx || !seed || !ticket || (!data && len)) return EH_E_INVALID;
   if (!ctx->configured) { ctx->err = "configure first"; return EH_E_STATE; }
   std::lock_guard<std::recursive_mutex> g(ctx->co_lock);
-  const size_t d0 = ctx->co_data.size(), o0 = ctx->co_off.size(), s0 = ctx->co_seeds.size(), t0 = ctx->co_tickets.size();
+  if (profile >= ctx->profiles.size()) { ctx->err = "no profile " + std::to_string(profile) + " (eh_profile_count = " + std::to_string(ctx->profiles.size()) + ")"; return EH_E_INVALID; }
+  const size_t d0 = ctx->co_data.size(), o0 = ctx->co_off.size(), s0 = ctx->co_seeds.size(), t0 = ctx->co_tickets.size(), p0 = ctx->co_profile.size();
   const uint64_t mine = ctx->co_next_ticket;
   try {
     ctx->co_data.insert(ctx->co_data.end(), data, data + len);
     ctx->co_off.push_back(ctx->co_data.size());
     ctx->co_seeds.insert(ctx->co_seeds.end(), seed, seed + 3);
+    ctx->co_profile.push_back(profile);
     ctx->co_tickets.push_back(mine);
-  } catch (const std::bad_alloc&) { ctx->co_data.resize(d0); ctx->co_off.resize(o0); ctx->co_seeds.resize(s0); ctx->co_tickets.resize(t0); return EH_E_NOMEM; }
+  } catch (const std::bad_alloc&) { ctx->co_data.resize(d0); ctx->co_off.resize(o0); ctx->co_seeds.resize(s0); ctx->co_profile.resize(p0); ctx->co_tickets.resize(t0); return EH_E_NOMEM; }
   ctx->co_next_ticket++;                                  // (before any launch: co_collect lets other submitters in)
   if (ctx->co_tickets.size() >= ctx->co_flush_cases || ctx->co_data.size() >= ctx->co_flush_bytes) {
     int rc = co_launch(ctx);
@@ -2026,6 +2135,7 @@ int eh_cancel(eh_ctx* ctx, uint64_t ticket) {
     ctx->co_off.erase(ctx->co_off.begin() + i + 1);
     for (size_t k = i + 1; k < ctx->co_off.size(); k++) ctx->co_off[k] -= b - a;
     ctx->co_seeds.erase(ctx->co_seeds.begin() + 3 * i, ctx->co_seeds.begin() + 3 * i + 3);
+    ctx->co_profile.erase(ctx->co_profile.begin() + i);
     ctx->co_tickets.erase(ctx->co_tickets.begin() + i);
     return EH_OK;
   }
@@ -2446,6 +2556,7 @@ int eh_last_kernel_ms(eh_ctx* ctx, float* ms) {
 
 // ---- uniqueness filter (csrc/eh_unique.h) -----------------------------------------------------------------------------------------
 static_assert(UQ_PIECE == EH_UNIQUE_PIECE_BYTES, "the header documents the piece size");
+static_assert(MAX_PROFILES == EH_MAX_PROFILES && sizeof(ProfileCfg) % 4 == 0, "the header documents the size of the profile table");
 // Device buffers for n cases and up to `pieces` pieces; they belong to the context and are reused while they fit.
 static int uq_ensure(eh_ctx* ctx, uint64_t n, uint64_t pieces, uint64_t slots) {
   if (n > ctx->uq_case_cap) {

@@ -37,7 +37,10 @@ ABI_SYMBOLS = [
     "eh_comm_unique_id", "eh_comm_init", "eh_comm_init_local", "eh_comm_destroy", "eh_corpus_broadcast", "eh_corpus_allgather",
     "eh_corpus_broadcast_local", "eh_device_count", "eh_meta_atom_count", "eh_meta_atom_name", "eh_batch_done",
     "eh_result_digests", "eh_result_unique", "eh_result_download_select", "eh_selftest_unique",
+    "eh_profile_add", "eh_profile_count", "eh_fuzz_calls_profiled", "eh_submit_profiled",
 ]
+
+MAX_PROFILES = 1024   # EH_MAX_PROFILES
 
 
 class EhOptions(C.Structure):
@@ -109,6 +112,10 @@ def load_library():
     lib.eh_coalesce_limits.argtypes = [vp, C.c_uint64, C.c_uint64]
     lib.eh_submit.argtypes = [vp, vp, C.c_uint64, i64p, u64p]
     lib.eh_flush.argtypes = [vp]
+    lib.eh_profile_add.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_double, C.POINTER(C.c_uint32)]
+    lib.eh_profile_count.argtypes = [vp, C.POINTER(C.c_uint32)]
+    lib.eh_fuzz_calls_profiled.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64, vp]
+    lib.eh_submit_profiled.argtypes = [vp, vp, C.c_uint64, i64p, C.c_uint32, u64p]
     lib.eh_meta_atom_name.restype = C.c_char_p
     lib.eh_meta_atom_name.argtypes = [C.c_int]
     lib.eh_comm_unique_id.argtypes = [vp]
@@ -306,11 +313,32 @@ class Engine:
         self._chk(self.lib.eh_fuzz_batch(self.h, s, first_case, corpus_first, n, C.c_void_p(stream)))
         self.last_n = n
 
-    def fuzz_calls(self, seeds, corpus_first=0, stream=0):
+    def fuzz_calls(self, seeds, profiles=None, corpus_first=0, stream=0):
+        """case i is its own run with seeds[i]; profiles (optional): the option profile id of every case (profile_add; 0 = what
+        configure was given) - eh_fuzz_calls_profiled"""
         seeds = np.ascontiguousarray(seeds, dtype=np.int64).reshape(-1)
         n = seeds.size // 3
-        self._chk(self.lib.eh_fuzz_calls(self.h, seeds.ctypes.data, corpus_first, n, C.c_void_p(stream)))
+        if profiles is None:
+            self._chk(self.lib.eh_fuzz_calls(self.h, seeds.ctypes.data, corpus_first, n, C.c_void_p(stream)))
+        else:
+            ids = np.ascontiguousarray(profiles, dtype=np.uint32).reshape(-1)
+            if ids.size != n:
+                raise ValueError("fuzz_calls: %d profile ids for %d seeds" % (ids.size, n))
+            self._chk(self.lib.eh_fuzz_calls_profiled(self.h, seeds.ctypes.data, ids.ctypes.data, corpus_first, n, C.c_void_p(stream)))
         self.last_n = n
+
+    # ---- option profiles: mutations / patterns / blockscale per case of one launch (eh_profile_add)
+    def profile_add(self, mutations=None, patterns=None, blockscale=1.0):
+        """-> id of the profile with these options (an equal one is found again, not added); 0 is what configure was given"""
+        pid = C.c_uint32()
+        self._chk(self.lib.eh_profile_add(self.h, mutations.encode() if mutations is not None else None,
+                                          patterns.encode() if patterns is not None else None, float(blockscale), C.byref(pid)))
+        return pid.value
+
+    def profile_count(self):
+        n = C.c_uint32()
+        self._chk(self.lib.eh_profile_count(self.h, C.byref(n)))
+        return n.value
 
     def reserve(self, max_cases):
         self._chk(self.lib.eh_reserve(self.h, max_cases))
@@ -533,12 +561,15 @@ class Engine:
     def coalesce_limits(self, flush_cases, flush_bytes):
         self._chk(self.lib.eh_coalesce_limits(self.h, flush_cases, flush_bytes))
 
-    def submit(self, data, seed):
-        """one erlamsa_app:fuzz(Bin, #{seed => Seed}) request -> ticket"""
+    def submit(self, data, seed, profile=0):
+        """one erlamsa_app:fuzz(Bin, #{seed => Seed}) request, run under option profile `profile` (profile_add) -> ticket"""
         b = bytes(data)
         t = C.c_uint64()
         buf = (C.c_char * max(len(b), 1)).from_buffer_copy(b or b"\0")
-        self._chk(self.lib.eh_submit(self.h, C.cast(buf, C.c_void_p), len(b), (C.c_int64 * 3)(*seed), C.byref(t)))
+        if profile == 0:
+            self._chk(self.lib.eh_submit(self.h, C.cast(buf, C.c_void_p), len(b), (C.c_int64 * 3)(*seed), C.byref(t)))
+        else:
+            self._chk(self.lib.eh_submit_profiled(self.h, C.cast(buf, C.c_void_p), len(b), (C.c_int64 * 3)(*seed), profile, C.byref(t)))
         return t.value
 
     def flush(self):
@@ -560,7 +591,7 @@ class Engine:
                 cap = int(n.value)
                 continue
             self._chk(rc)
-            return st.value, bytes(out[:n.value])
+            return st.value, C.string_at(out, n.value)
 
     def result_device(self):
         d, o, l, s = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()

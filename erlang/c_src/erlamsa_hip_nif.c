@@ -11,6 +11,8 @@
  *       case I is its own fuzzer/1 run with n = 1 and the I-th seed: erlamsa_app:fuzz/2      (eh_fuzz_calls)
  *   Status: enum eh_case_status.  Both run on a dirty I/O scheduler: one call = one GPU batch.
  *   submit_nif / flush_nif / poll_nif: request coalescing, see below.
+ *   profile_add_nif / submit_profiled_nif / fuzz_calls_profiled_nif: requests with their own mutations / patterns / blockscale
+ *       (erlamsa_esi.erl:30-68) in one launch, see "option profiles" below.
  *   Several GPUs (ABI 7, include/erlamsa_hip.h "multi-GPU"), see the end of this file:
  *     device_count() / load_corpus_nif / fuzz_range_nif                       a corpus that stays loaded, case ranges of it
  *     comm_init_local_nif([Ctx]) / broadcast_local_nif([Ctx], Root)           one BEAM node, one context per GPU
@@ -125,10 +127,11 @@ static int configure_if_changed(ctx_res* r, const opt_key* k) {
   return rc;
 }
 
-/* mode 0: argv = Ctx, Opts, Seed, FirstCase, Bins;  mode 1: argv = Ctx, Opts, Seeds, Bins */
+/* mode 0: argv = Ctx, Opts, Seed, FirstCase, Bins;  mode 1: argv = Ctx, Opts, Seeds, Bins;  mode 2: argv = Ctx, Opts, Seeds, Profiles, Bins */
 static ERL_NIF_TERM run(ErlNifEnv* env, const ERL_NIF_TERM argv[], int mode) {
   ctx_res* r; unsigned n = 0, ns = 0; ErlNifUInt64 first = 1; opt_key k;
-  ERL_NIF_TERM bins = argv[mode == 0 ? 4 : 3];
+  ERL_NIF_TERM bins = argv[mode == 1 ? 3 : 4];
+  uint32_t* profs = NULL;
   if (!enif_get_resource(env, argv[0], ctx_type, (void**)&r) || !enif_is_map(env, argv[1]) || !enif_get_list_length(env, bins, &n))
     return enif_make_badarg(env);
   if (!read_opts(env, argv[1], &k)) return enif_make_badarg(env);
@@ -149,6 +152,16 @@ static ERL_NIF_TERM run(ErlNifEnv* env, const ERL_NIF_TERM argv[], int mode) {
       if (!enif_get_tuple(env, head, &arity, &st) || arity != 3) { free(seeds); return enif_make_badarg(env); }
       for (int j = 0; j < 3; j++) { if (!enif_get_int64(env, st[j], &v)) { free(seeds); return enif_make_badarg(env); } seeds[3 * i + j] = v; }
     }
+    if (mode == 2) {                             /* the profile id of every case (profile_add_nif) */
+      unsigned np = 0, q = 0; ErlNifUInt64 id;
+      if (!enif_get_list_length(env, argv[3], &np) || np != n) { free(seeds); return enif_make_badarg(env); }
+      profs = malloc((size_t)(n ? n : 1) * sizeof(uint32_t));
+      if (!profs) { free(seeds); return mk_err_atom(env, "enomem"); }
+      for (ERL_NIF_TERM l = argv[3]; enif_get_list_cell(env, l, &head, &l); q++) {
+        if (!enif_get_uint64(env, head, &id) || id >= EH_MAX_PROFILES) { free(seeds); free(profs); return enif_make_badarg(env); }
+        profs[q] = (uint32_t)id;
+      }
+    }
   }
   /* pack the inputs: binaries are read-only and not retained past the call */
   off = malloc(((size_t)n + 1) * sizeof(uint64_t));
@@ -167,9 +180,12 @@ static ERL_NIF_TERM run(ErlNifEnv* env, const ERL_NIF_TERM argv[], int mode) {
   }
   enif_mutex_lock(r->lock);                      /* one batch at a time per context */
   {
-    int rc = configure_if_changed(r, &k);
+    /* mode 2: the ids belong to the configuration they were made under - another one would drop them (eh_configure) */
+    int rc = mode == 2 && !(r->configured && memcmp(&r->key, &k, sizeof(k)) == 0) ? EH_E_STATE : configure_if_changed(r, &k);
+    if (rc == EH_E_STATE && mode == 2) { ret = mk_err_atom(env, "stale_profile"); enif_mutex_unlock(r->lock); goto done; }
     if (!rc) rc = eh_corpus_upload(r->ctx, data, off, n);
-    if (!rc) rc = mode == 0 ? eh_fuzz_batch(r->ctx, (const int64_t*)seed, first, 0, n, NULL) : eh_fuzz_calls(r->ctx, seeds, 0, n, NULL);
+    if (!rc) rc = mode == 0 ? eh_fuzz_batch(r->ctx, (const int64_t*)seed, first, 0, n, NULL)
+                : mode == 1 ? eh_fuzz_calls(r->ctx, seeds, 0, n, NULL) : eh_fuzz_calls_profiled(r->ctx, seeds, profs, 0, n, NULL);
     uint64_t in_b = 0, out_b = 0, nc = 0;
     if (!rc) rc = eh_result_totals(r->ctx, &in_b, &out_b, &nc);
     if (!rc) {
@@ -190,7 +206,7 @@ static ERL_NIF_TERM run(ErlNifEnv* env, const ERL_NIF_TERM argv[], int mode) {
   }
   ret = enif_make_tuple2(env, enif_make_atom(env, "ok"), ret);
 done:
-  free(seeds); free(off); free(data); free(out); free(status);
+  free(seeds); free(profs); free(off); free(data); free(out); free(status);
   return ret;
 }
 
@@ -212,6 +228,52 @@ static ERL_NIF_TERM nif_submit(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv
   if (!rc) rc = configure_if_changed(r, &k);
   if (!rc) rc = eh_submit(r->ctx, b.data, b.size, seed, &ticket);
   ERL_NIF_TERM ret = rc ? mk_error(env, r->ctx, rc) : enif_make_tuple2(env, enif_make_atom(env, "ok"), enif_make_uint64(env, ticket));
+  enif_mutex_unlock(r->lock);
+  return ret;
+}
+/* Option profiles (eh_profile_add / eh_submit_profiled / eh_fuzz_calls_profiled): the mutations, patterns and blockscale erlamsa_esi
+ * reads from every request (erlamsa_esi.erl:30-68).  Opts are the SERVICE's options, the ones the context is configured with; a
+ * profile id is valid while they stay the same (eh_configure drops all profiles).
+ *   profile_add_nif(Ctx, Opts, Mutations, Patterns, Blockscale) -> {ok, Id} | {error, nomem} | {error, Reason}
+ *       Mutations / Patterns: the strings of Opts' keys of the same name, or the atom default.  Interned: equal options, equal id;
+ *       the service's own options give 0.  nomem: EH_MAX_PROFILES distinct profiles exist - run the request on BEAM.
+ *   submit_profiled_nif(Ctx, Opts, {A,B,C}, Bin, Id) -> {ok, Ticket} | {error, stale_profile} | {error, Reason}
+ *   fuzz_calls_profiled_nif(Ctx, Opts, [{A,B,C}], [Id], [binary()]) -> as fuzz_calls_nif, case I under the I-th profile */
+static int get_opt_str(ErlNifEnv* env, ERL_NIF_TERM t, char* buf, unsigned n, const char** out) {
+  if (enif_compare(t, enif_make_atom(env, "default")) == 0) { *out = NULL; return 1; }
+  if (enif_get_string(env, t, buf, n, ERL_NIF_LATIN1) <= 0) return 0;
+  *out = buf;
+  return 1;
+}
+static ERL_NIF_TERM nif_profile_add(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  (void)argc; ctx_res* r; opt_key k; char muts[OPT_STR], pats[256]; const char* m = NULL; const char* p = NULL; double bs = 1.0;
+  if (!enif_get_resource(env, argv[0], ctx_type, (void**)&r) || !enif_is_map(env, argv[1]) || !read_opts(env, argv[1], &k) ||
+      !get_opt_str(env, argv[2], muts, sizeof(muts), &m) || !get_opt_str(env, argv[3], pats, sizeof(pats), &p) || !enif_get_double(env, argv[4], &bs))
+    return enif_make_badarg(env);
+  enif_mutex_lock(r->lock);
+  uint32_t id = 0;
+  int rc = EH_OK;
+  if (r->configured && memcmp(&r->key, &k, sizeof(k)) != 0) rc = eh_flush(r->ctx);      /* as submit_nif: what is pending keeps its options */
+  if (!rc) rc = configure_if_changed(r, &k);
+  if (!rc) rc = eh_profile_add(r->ctx, m, p, bs, &id);
+  ERL_NIF_TERM ret = rc == EH_E_NOMEM ? mk_err_atom(env, "nomem") : rc ? mk_error(env, r->ctx, rc) : enif_make_tuple2(env, enif_make_atom(env, "ok"), enif_make_uint64(env, id));
+  enif_mutex_unlock(r->lock);
+  return ret;
+}
+static ERL_NIF_TERM nif_submit_profiled(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  (void)argc; ctx_res* r; opt_key k; const ERL_NIF_TERM* st; int arity; ErlNifBinary b; ErlNifSInt64 v; int64_t seed[3]; ErlNifUInt64 id;
+  if (!enif_get_resource(env, argv[0], ctx_type, (void**)&r) || !enif_is_map(env, argv[1]) || !read_opts(env, argv[1], &k) ||
+      !enif_get_tuple(env, argv[2], &arity, &st) || arity != 3 || !enif_inspect_binary(env, argv[3], &b) || !enif_get_uint64(env, argv[4], &id) || id >= EH_MAX_PROFILES)
+    return enif_make_badarg(env);
+  for (int j = 0; j < 3; j++) { if (!enif_get_int64(env, st[j], &v)) return enif_make_badarg(env); seed[j] = v; }
+  enif_mutex_lock(r->lock);
+  uint64_t ticket = 0;
+  ERL_NIF_TERM ret;
+  if (!(r->configured && memcmp(&r->key, &k, sizeof(k)) == 0)) ret = mk_err_atom(env, "stale_profile");   /* the id was made under other options */
+  else {
+    int rc = eh_submit_profiled(r->ctx, b.data, b.size, seed, (uint32_t)id, &ticket);
+    ret = rc ? mk_error(env, r->ctx, rc) : enif_make_tuple2(env, enif_make_atom(env, "ok"), enif_make_uint64(env, ticket));
+  }
   enif_mutex_unlock(r->lock);
   return ret;
 }
@@ -262,6 +324,7 @@ static ERL_NIF_TERM nif_poll(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]
 
 static ERL_NIF_TERM nif_fuzz_batch(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { (void)argc; return run(env, argv, 0); }
 static ERL_NIF_TERM nif_fuzz_calls(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { (void)argc; return run(env, argv, 1); }
+static ERL_NIF_TERM nif_fuzz_calls_profiled(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { (void)argc; return run(env, argv, 2); }
 
 /* ---- several GPUs (ABI 7) -----------------------------------------------------------------------------------------------------
  * The corpus stays loaded on the context(s); a process per device then runs its contiguous range of the case numbers
@@ -413,6 +476,9 @@ static ErlNifFunc funcs[] = {
   {"fuzz_batch_nif", 5, nif_fuzz_batch, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"fuzz_calls_nif", 4, nif_fuzz_calls, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"submit_nif", 4, nif_submit, ERL_NIF_DIRTY_JOB_IO_BOUND},
+  {"profile_add_nif", 5, nif_profile_add, ERL_NIF_DIRTY_JOB_IO_BOUND},
+  {"submit_profiled_nif", 5, nif_submit_profiled, ERL_NIF_DIRTY_JOB_IO_BOUND},
+  {"fuzz_calls_profiled_nif", 5, nif_fuzz_calls_profiled, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"flush_nif", 1, nif_flush, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"poll_nif", 2, nif_poll, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"write_files_nif", 3, nif_write_files, ERL_NIF_DIRTY_JOB_IO_BOUND},

@@ -16,6 +16,7 @@
 -module(erlamsa_hip).
 -export([init/0, open/1, fuzz_batch/2, fuzz_calls/2, fuzz_batch_nif/5, fuzz_calls_nif/4, capabilities/0, fuzzer/3]).
 -export([submit/3, flush/1, poll/2, submit_nif/4, flush_nif/1, poll_nif/2]).
+-export([profile_add/4, submit/4, fuzz_calls/3, co_ctx/1, profile_add_nif/5, submit_profiled_nif/5, fuzz_calls_profiled_nif/5]).
 -export([write_files/3, write_files_nif/3]).
 -export([meta_terms/1, meta_terms/3, meta_print/2, meta_nif/2, meta_atoms_nif/0]).
 -export([fuzz_batch_multi/2, open_all/0, device_count/0, load_corpus_nif/2, fuzz_range_nif/6, comm_init_local_nif/1, broadcast_local_nif/2,
@@ -30,6 +31,9 @@ open(_Device) -> erlang:nif_error(nif_not_loaded).
 fuzz_batch_nif(_Ctx, _Opts, _Seed, _FirstCase, _Bins) -> erlang:nif_error(nif_not_loaded).
 fuzz_calls_nif(_Ctx, _Opts, _Seeds, _Bins) -> erlang:nif_error(nif_not_loaded).
 submit_nif(_Ctx, _Opts, _Seed, _Bin) -> erlang:nif_error(nif_not_loaded).
+profile_add_nif(_Ctx, _Opts, _Mutations, _Patterns, _Blockscale) -> erlang:nif_error(nif_not_loaded).
+submit_profiled_nif(_Ctx, _Opts, _Seed, _Bin, _Profile) -> erlang:nif_error(nif_not_loaded).
+fuzz_calls_profiled_nif(_Ctx, _Opts, _Seeds, _Profiles, _Bins) -> erlang:nif_error(nif_not_loaded).
 flush_nif(_Ctx) -> erlang:nif_error(nif_not_loaded).
 poll_nif(_Ctx, _Ticket) -> erlang:nif_error(nif_not_loaded).
 write_files_nif(_Ctx, _Template, _FirstN) -> erlang:nif_error(nif_not_loaded).
@@ -236,6 +240,38 @@ submit(Bin, Seed, Dict) ->
     end.
 flush(Dict) -> flush_nif(co_ctx(Dict)).
 poll(Ticket, Dict) -> poll_nif(co_ctx(Dict), Ticket).
+
+%% ---- option profiles: the mutations, patterns and blockscale erlamsa_esi reads from EVERY request (erlamsa_esi.erl:30-68), many of
+%% them in one launch (include/erlamsa_hip.h eh_profile_add).  Dict is the SERVICE's options map, the one the context is configured
+%% with; a profile id is valid on that context while Dict's engine options stay the same (another configuration drops all
+%% profiles: submit/4 then answers {error, stale_profile}).
+%%   profile_add(Mutations, Patterns, Blockscale, Dict) -> {ok, Id} | {error, nomem} | {error, Reason}
+%%       Mutations / Patterns: [{Name, Pri}] as Dict's keys of the same name, or the atom default.  Interned on the engine's side:
+%%       call it for every request.  0 is Dict's own options.  nomem: the table is full, this request runs on BEAM.
+%%   submit(Bin, Seed, Profile, Dict) -> {ok, Ticket}: submit/3 under that profile; poll/2 and flush/1 as before.
+%%   fuzz_calls(Calls, Profiles, Dict): fuzz_calls/2 with the I-th call under the I-th profile id.
+%% All three use the coalescer's context (co_ctx/1; #{hip_co_ctx => C} names another one).
+profile_add(Mutations, Patterns, Blockscale, Dict) ->
+    case host_only(Dict) of
+        [] -> profile_add_nif(co_ctx(Dict), opts(Dict), profile_actions(Mutations), profile_actions(Patterns), float(Blockscale));
+        Keys -> {error, {unsupported, Keys}}
+    end.
+profile_actions(default) -> default;
+profile_actions(L) -> actions(L).
+
+submit(Bin, Seed, Profile, Dict) ->
+    case host_only(Dict) of
+        [] -> submit_profiled_nif(co_ctx(Dict), opts(Dict), Seed, Bin, Profile);
+        Keys -> {error, {unsupported, Keys}}
+    end.
+
+fuzz_calls(Calls, Profiles, Dict) ->
+    case host_only(Dict) of
+        [] ->
+            {Bins, Seeds} = lists:unzip(Calls),
+            split(fuzz_calls_profiled_nif(co_ctx(Dict), opts(Dict), Seeds, Profiles, Bins), 1, 0);
+        Keys -> {error, {unsupported, Keys}}
+    end.
 
 co_ctx(#{hip_co_ctx := C}) -> C;
 co_ctx(Dict) -> shared_ctx(erlamsa_hip_co_ctx, Dict).

@@ -20,6 +20,8 @@
  *                          (erlamsa_app.erl:255-263), i.e. what erlamsa_esi:call_fuzzer/3 ->
  *                          erlamsa_fsupervisor:get_fuzzing_output/1 does per HTTP request
  *                          (erlamsa_esi.erl:86-95, erlamsa_fsupervisor.erl:60-86)
+ *   eh_profile_add /    <- the per-request `mutations`, `patterns`, `blockscale` of erlamsa_esi:parse_headers/2 and
+ *   eh_*_profiled          parse_json_map_elem/3 (erlamsa_esi.erl:30-68,85-95): cases of one launch under different option profiles
  *   eh_result_*         <- the [binary()] returned by fuzzer/1 / the binary returned by
  *                          erlamsa_app:fuzz/2 (per-case status lets the shim rebuild
  *                          record_result/2's dropping of <<>> results, erlamsa_main.erl:120-122)
@@ -231,6 +233,31 @@ int eh_poll(eh_ctx* ctx, uint64_t ticket, uint8_t* out, uint64_t cap, uint64_t* 
 /* Gives a ticket up: a request that has not been launched leaves its batch, a launched one is dropped when the batch is
  * collected, a finished one is freed (a service whose client timed out or died calls this so that results do not pile up). */
 int eh_cancel(eh_ctx* ctx, uint64_t ticket);
+
+/* ---- option profiles: mutations, patterns and blockscale per REQUEST, many of them in one launch (added within ABI 8).
+ * Reference counterpart: erlamsa_esi:parse_headers/2 and parse_json_map_elem/3 (erlamsa_esi.erl:30-68) read `mutations`, `patterns`,
+ * `blockscale` and `seed` from every HTTP request, and call_fuzzer/3 (erlamsa_esi.erl:85-95) hands them to
+ * erlamsa_fsupervisor:get_fuzzing_output/1 request by request.  A PROFILE is those three keys without the seed; everything else -
+ * generators, the SSRF endpoint, max_case_bytes, max_case_work, flags, pool sizes, fuse_stream_min - stays the context's.
+ *
+ * eh_profile_add    parses the strings exactly as eh_configure does (NULL = the reference's defaults, blockscale 0 = 1.0) and returns
+ *                   the id of the profile.  Profiles are interned by what they parse to: "bd,bf" and "bd=1,bf=1" are one profile, and
+ *                   options equal to the context's own give id 0 - a service can call this for every request.  Allowed while requests
+ *                   are pending or a batch is in flight: ids only grow, existing entries never change, the device copy is completed
+ *                   before the next launch.  EH_E_INVALID an unknown name, a bad priority or an empty pattern list; EH_E_UNSUPPORTED a
+ *                   mutator or pattern that does not run on the GPU; EH_E_NOMEM when EH_MAX_PROFILES distinct profiles exist (the
+ *                   request then runs elsewhere - or eh_configure starts a new table); EH_E_STATE before eh_configure.
+ * eh_profile_count  profiles of the context, profile 0 included (0 before eh_configure).
+ * Profile 0 is what eh_configure was given.  eh_configure drops all others: their ids become invalid.
+ * eh_fuzz_calls_profiled  eh_fuzz_calls with case i run under profile[i] (n ids, host pointer); eh_fuzz_calls is this call with all ids 0.
+ * eh_submit_profiled      eh_submit under the given profile; eh_submit is this call with profile 0.  Requests of different profiles
+ *                   share one launch.
+ * An id >= eh_profile_count is EH_E_INVALID in both, and nothing is queued or launched. */
+#define EH_MAX_PROFILES 1024
+int eh_profile_add(eh_ctx* ctx, const char* mutations, const char* patterns, double blockscale, uint32_t* id);
+int eh_profile_count(eh_ctx* ctx, uint32_t* n);
+int eh_fuzz_calls_profiled(eh_ctx* ctx, const int64_t* seeds, const uint32_t* profile, uint64_t corpus_first, uint64_t n, void* stream);
+int eh_submit_profiled(eh_ctx* ctx, const uint8_t* data, uint64_t len, const int64_t seed[3], uint32_t profile, uint64_t* ticket);
 
 /* Device-side view of the last batch: out_data[out_off[i] .. out_off[i]+out_len[i]) is the
  * output of case i.  Pointers stay valid until the next eh_fuzz_* call on this context. */
