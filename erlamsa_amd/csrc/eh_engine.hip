@@ -1179,14 +1179,39 @@ using namespace eh;
 template <class T> struct DevPtr { T* p; template <class U> operator U() const { return (U)p; } };
 template <class T> static inline DevPtr<T> dp(T* p) { return DevPtr<T>{p}; }
 
+// The owner of a device allocation, and the only place of the host side that allocates or frees device memory: the pointer and its
+// capacity (in elements) change only together, so after a failed growth the buffer is empty, not stale.  Contents are never kept.
+template <class T> struct DevBuf {
+  T* p = nullptr;
+  uint64_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr; cap = 0;
+  }
+  hipError_t reset(uint64_t n) {                        // exactly n elements, whatever it held
+    release();
+    hipError_t e = hipMalloc(&p, n * sizeof(T));
+    if (e == hipSuccess) cap = n; else p = nullptr;
+    return e;
+  }
+  hipError_t grow(uint64_t n) { return n <= cap ? hipSuccess : reset(n); }
+  void swap(DevBuf& o) { std::swap(p, o.p); std::swap(cap, o.cap); }
+  operator T*() const { return p; }
+};
+template <class T> static inline DevPtr<T> dp(const DevBuf<T>& b) { return DevPtr<T>{b.p}; }
+
 // the work-area pool of a device (see pool_acquire)
 struct DevPool {
   int device = 0; uint64_t work_cap = 0, big = 0, pool_bytes_opt = 0;
   int refs = 0;
   int ntiers = 0;                                       // tiers 1..ntiers
-  uint8_t* base[POOL_TIERS + 1] = {}; uint64_t stride[POOL_TIERS + 1] = {}, cap[POOL_TIERS + 1] = {}; uint32_t cnt[POOL_TIERS + 1] = {};
-  uint32_t* d_rings = nullptr; uint32_t* ring[POOL_TIERS + 1] = {}; unsigned long long* d_ctr = nullptr;
-  CoBoard* d_board = nullptr;                           // cooperative execution: the board every context of the device posts on (eh_common.h)
+  DevBuf<uint8_t> base[POOL_TIERS + 1]; uint64_t stride[POOL_TIERS + 1] = {}, cap[POOL_TIERS + 1] = {}; uint32_t cnt[POOL_TIERS + 1] = {};
+  DevBuf<uint32_t> d_rings; uint32_t* ring[POOL_TIERS + 1] = {}; DevBuf<unsigned long long> d_ctr;
+  DevBuf<CoBoard> d_board;                              // cooperative execution: the board every context of the device posts on (eh_common.h)
 };
 
 struct eh_ctx {
@@ -1199,36 +1224,37 @@ struct eh_ctx {
   uint64_t fuse_stream_min = 16384, pool_bytes_opt = 0, dl_chunk = 256ull << 20;   // eh_options (ABI 4)
   uint32_t max_slots_opt = 0, flags = 0;
   int needs_paths = 0;                                  // corpus entries the configured generators need (file: 1, jump: 2)
-  KParams* d_params = nullptr;                          // argument block of eh_mutate_kernel
+  DevBuf<KParams> d_params;                             // argument block of eh_mutate_kernel
   // eh_result_download: case-ordered chunks are gathered on the device into two bounce buffers; chunk k goes over PCIe
   // while chunk k+1 is gathered
-  uint8_t* d_bounce[2] = {nullptr, nullptr}; uint64_t bounce_cap = 0, bounce_chunk = 0; hipStream_t dl_gather = nullptr, dl_copy = nullptr;
+  DevBuf<uint8_t> d_bounce[2]; uint64_t bounce_chunk = 0; hipStream_t dl_gather = nullptr, dl_copy = nullptr;
   hipEvent_t ev_g[2] = {nullptr, nullptr}, ev_c[2] = {nullptr, nullptr};
-  uint8_t* d_out2 = nullptr; uint64_t out2_cap = 0;   // EH_FLAG_ORDERED_OUTPUT: second arena (case order)
-  uint64_t* d_ord = nullptr; uint64_t ord_cap = 0;      // ordered offsets (n + 1)
+  DevBuf<uint8_t> d_out2;                               // EH_FLAG_ORDERED_OUTPUT: second arena (case order)
+  DevBuf<uint64_t> d_ord;                               // ordered offsets (n + 1)
   bool ordered = false;                                 // the last batch's results are in case order
-  // corpus
-  uint8_t* d_corpus = nullptr; uint64_t* d_coff = nullptr; bool own_corpus = false;
-  uint64_t own_corpus_cap = 0, own_coff_cap = 0;         // capacity of the owned buffers: eh_corpus_upload reuses them when they fit
+  // corpus: the current one, in the context's own buffers (upload, collectives: reused while they fit) or the caller's (eh_corpus_attach)
+  uint8_t* d_corpus = nullptr; uint64_t* d_coff = nullptr;
+  DevBuf<uint8_t> own_corpus; DevBuf<uint64_t> own_coff;
   uint64_t n_corpus = 0, corpus_bytes = 0;
   std::vector<uint64_t> h_coff;  // host copy of offsets (for totals)
   // work areas: a pool shared by every context of the device with the same sizes (DevPool below)
   DevPool* pool = nullptr;
-  uint8_t* d_slots = nullptr; uint64_t slot_stride = 0, slot_cap = 0; uint32_t nslots = 0;   // a slot per workgroup of a batch
+  DevBuf<uint8_t> d_slots; uint64_t slot_stride = 0, slot_cap = 0; uint32_t nslots = 0;   // a slot per workgroup of a batch
   uint64_t big_case_bytes = 0;
-  // outputs
-  uint8_t* d_out = nullptr; uint64_t out_cap = 0;
-  uint64_t* d_off = nullptr; uint64_t* d_len = nullptr; int32_t* d_status = nullptr; uint64_t* d_draws = nullptr; int32_t* d_lastm = nullptr; uint64_t* d_cycles = nullptr; uint64_t* d_peak = nullptr; uint64_t* d_toff = nullptr; uint32_t* d_tlen = nullptr;
-  uint64_t res_cap = 0;
-  unsigned long long* d_counters = nullptr;  // [0] ticket, [1] out cursor, [2] input bytes, [3] cases done, [4] lingering wavefronts, [5] output bytes, [6] workgroups that left, [8, 264) EH_PROF, [264, 270) cases by status
+  // outputs: the arena, and an entry per case in each of the result arrays
+  DevBuf<uint8_t> d_out;
+  DevBuf<uint64_t> d_off, d_len, d_draws, d_cycles, d_peak, d_toff;
+  DevBuf<int32_t> d_status, d_lastm;
+  DevBuf<uint32_t> d_tlen;
+  DevBuf<unsigned long long> d_counters;  // [0] ticket, [1] out cursor, [2] input bytes, [3] cases done, [4] lingering wavefronts, [5] output bytes, [6] workgroups that left, [8, 264) EH_PROF, [264, 270) cases by status
   unsigned long long* h_sum = nullptr; uint64_t batch_seq = 0;   // page-locked: the last batch's totals, written by the kernel (KParams::summary_out)
-  RunState* d_run = nullptr;
-  int64_t* d_seeds = nullptr; uint64_t seeds_cap = 0;  // mode 1: 3 x seeds_cap seeds, then seeds_cap profile ids (uint32) in the same allocation
+  DevBuf<RunState> d_run;
+  DevBuf<uint8_t> d_seeds;                              // mode 1, SEED_ROW bytes per case: three int64 seeds for every case, then a uint32 profile id for every case
   // option profiles (eh_profile_add), guarded by co_lock.  profiles[0] = what eh_configure was given; entries are never changed once made,
   // ids only grow until the next eh_configure.  The device table has room for all EH_MAX_PROFILES; entries [0, profiles_on_device) of it
   // are current, the rest is copied before the next profiled launch (launches of one context run one after the other).
   std::vector<ProfileCfg> profiles; std::unordered_map<std::string, uint32_t> profile_index;
-  ProfileCfg* d_profiles = nullptr; uint32_t profiles_on_device = 0;
+  DevBuf<ProfileCfg> d_profiles; uint32_t profiles_on_device = 0;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   // request coalescing (eh_submit / eh_flush / eh_poll)
   std::recursive_mutex co_lock;
@@ -1246,11 +1272,11 @@ struct eh_ctx {
   uint64_t last_n = 0, last_in_bytes = 0;
   bool have_result = false;
   // uniqueness filter (eh_unique.h): sized on first use, reused while they fit; results are cached per batch (batch_seq)
-  uint64_t* d_uq_digest = nullptr; uint64_t* d_uq_first = nullptr; uint64_t* d_uq_pfirst = nullptr; uint32_t* d_uq_flag = nullptr; uint64_t uq_case_cap = 0;
-  unsigned long long* d_uq_term = nullptr; uint64_t uq_term_cap = 0;         // a pair of CRCs per piece
-  unsigned long long* d_uq_tab = nullptr; uint64_t uq_tab_cap = 0;           // [0] unique cases, [1] their bytes, then owner[slots], rep[slots]
+  DevBuf<uint64_t> d_uq_digest, d_uq_first, d_uq_pfirst; DevBuf<uint32_t> d_uq_flag;
+  DevBuf<unsigned long long> d_uq_term;                                      // a pair of CRCs per piece
+  DevBuf<unsigned long long> d_uq_tab;                                       // [0] unique cases, [1] their bytes, then owner[slots], rep[slots]
   uint64_t uq_digest_seq = 0, uq_unique_seq = 0, uq_n_unique = 0, uq_bytes = 0;   // batch the device arrays / the two totals belong to (0: none)
-  uint64_t* d_sel = nullptr; uint64_t sel_cap = 0;                           // eh_result_download_select: offsets, lengths, destinations of the listed cases
+  DevBuf<uint64_t> d_sel;                                                    // eh_result_download_select: offsets, lengths, destinations of the listed cases
 };
 
 #define HIPCHK(ctx, call)                                                                             \
@@ -1341,30 +1367,26 @@ static int parse_profile(eh_ctx* ctx, const char* mutations, const char* pattern
 static std::string profile_key(const ProfileCfg& pc) { return std::string((const char*)&pc, sizeof(pc)); }
 
 // Device memory of a mode-1 launch of up to n cases: the seeds and, behind them, the cases' profile ids; and the profile table.
+const uint64_t SEED_ROW = 3 * sizeof(int64_t) + sizeof(uint32_t);
 static int ensure_seeds(eh_ctx* ctx, uint64_t n) {
-  if (!ctx->d_profiles) HIPCHK(ctx, hipMalloc(&ctx->d_profiles, MAX_PROFILES * sizeof(ProfileCfg)));
-  if (n <= ctx->seeds_cap) return EH_OK;
-  if (ctx->d_seeds) (void)hipFree(ctx->d_seeds);
-  ctx->d_seeds = nullptr; ctx->seeds_cap = 0;
-  HIPCHK(ctx, hipMalloc(&ctx->d_seeds, n * 24 + n * 4));
-  ctx->seeds_cap = n;
+  HIPCHK(ctx, ctx->d_profiles.grow(MAX_PROFILES));
+  HIPCHK(ctx, ctx->d_seeds.grow(n * SEED_ROW));
   return EH_OK;
 }
-static uint32_t* profile_ids_of(eh_ctx* ctx) { return (uint32_t*)(ctx->d_seeds + 3 * ctx->seeds_cap); }
+static int64_t* seeds_of(eh_ctx* ctx) { return (int64_t*)ctx->d_seeds.p; }
+static uint32_t* profile_ids_of(eh_ctx* ctx) { return (uint32_t*)(seeds_of(ctx) + 3 * (ctx->d_seeds.cap / SEED_ROW)); }
 
+// (each array has a capacity of its own: any prefix of the growths may have succeeded when one fails)
 static int ensure_results(eh_ctx* ctx, uint64_t n) {
-  if (n <= ctx->res_cap) return EH_OK;
-  if (ctx->d_off) { (void)hipFree(ctx->d_off); (void)hipFree(ctx->d_len); (void)hipFree(ctx->d_status); (void)hipFree(ctx->d_draws); (void)hipFree(ctx->d_lastm); (void)hipFree(ctx->d_cycles); (void)hipFree(ctx->d_peak); (void)hipFree(ctx->d_toff); (void)hipFree(ctx->d_tlen); }
-  HIPCHK(ctx, hipMalloc(&ctx->d_cycles, n * 8));
-  HIPCHK(ctx, hipMalloc(&ctx->d_peak, n * 8));
-  HIPCHK(ctx, hipMalloc(&ctx->d_toff, n * 8));
-  HIPCHK(ctx, hipMalloc(&ctx->d_tlen, n * 4));
-  HIPCHK(ctx, hipMalloc(&ctx->d_off, n * 8));
-  HIPCHK(ctx, hipMalloc(&ctx->d_len, n * 8));
-  HIPCHK(ctx, hipMalloc(&ctx->d_status, n * 4));
-  HIPCHK(ctx, hipMalloc(&ctx->d_draws, n * 8));
-  HIPCHK(ctx, hipMalloc(&ctx->d_lastm, n * 4));
-  ctx->res_cap = n;
+  HIPCHK(ctx, ctx->d_cycles.grow(n));
+  HIPCHK(ctx, ctx->d_peak.grow(n));
+  HIPCHK(ctx, ctx->d_toff.grow(n));
+  HIPCHK(ctx, ctx->d_tlen.grow(n));
+  HIPCHK(ctx, ctx->d_off.grow(n));
+  HIPCHK(ctx, ctx->d_len.grow(n));
+  HIPCHK(ctx, ctx->d_status.grow(n));
+  HIPCHK(ctx, ctx->d_draws.grow(n));
+  HIPCHK(ctx, ctx->d_lastm.grow(n));
   return EH_OK;
 }
 
@@ -1379,10 +1401,6 @@ static std::vector<DevPool*> g_pools;
 static void pool_free(DevPool* pl) {
   (void)hipSetDevice(pl->device);
   (void)hipDeviceSynchronize();
-  for (int t = 1; t <= pl->ntiers; t++) if (pl->base[t]) (void)hipFree(pl->base[t]);
-  if (pl->d_rings) (void)hipFree(pl->d_rings);
-  if (pl->d_ctr) (void)hipFree(pl->d_ctr);
-  if (pl->d_board) (void)hipFree(pl->d_board);
   delete pl;
 }
 static void pool_release(eh_ctx* ctx) {
@@ -1430,7 +1448,7 @@ static int pool_acquire(eh_ctx* ctx, uint64_t work_cap, uint64_t big, uint64_t p
     uint64_t cnt = pool_bytes / share_sum * SHARE[k == nt - 1 ? POOL_TIERS - 1 : k] / stride_t; if (cnt < 1) cnt = 1; if (cnt > 4096) cnt = 4096;
     if (ctx->cus < 64 && cnt > 2) cnt = 2;                                         // (the emulator)
     int t = pl->ntiers + 1;
-    for (; cnt >= 1; cnt /= 2) { e = hipMalloc(&pl->base[t], stride_t * cnt); if (e == hipSuccess) break; pl->base[t] = nullptr; }
+    for (; cnt >= 1; cnt /= 2) { e = pl->base[t].grow(stride_t * cnt); if (e == hipSuccess) break; }
     if (e != hipSuccess) break;
     pl->stride[t] = stride_t; pl->cap[t] = caps[k]; pl->cnt[t] = (uint32_t)cnt; pl->ntiers++;
   }
@@ -1438,7 +1456,7 @@ static int pool_acquire(eh_ctx* ctx, uint64_t work_cap, uint64_t big, uint64_t p
   for (int t = 1; t <= pl->ntiers; t++) nring += pl->cnt[t];
   std::vector<uint32_t> init(nring);
   std::vector<unsigned long long> ctr(64, 0ull);
-  if (hipMalloc(&pl->d_rings, nring * 4) != hipSuccess || hipMalloc(&pl->d_ctr, 64 * 8) != hipSuccess) { pool_free(pl); ctx->err = "work-area pool: out of device memory"; return EH_E_NOMEM; }
+  if (pl->d_rings.grow(nring) != hipSuccess || pl->d_ctr.grow(64) != hipSuccess) { pool_free(pl); ctx->err = "work-area pool: out of device memory"; return EH_E_NOMEM; }
   uint64_t o = 0;
   for (int t = 1; t <= pl->ntiers; t++) {
     pl->ring[t] = pl->d_rings + o;
@@ -1448,7 +1466,7 @@ static int pool_acquire(eh_ctx* ctx, uint64_t work_cap, uint64_t big, uint64_t p
   }
   if (hipMemcpy(pl->d_rings, init.data(), nring * 4, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(pl->d_ctr, ctr.data(), 64 * 8, hipMemcpyHostToDevice) != hipSuccess) { pool_free(pl); ctx->err = "work-area pool: hipMemcpy failed"; return EH_E_HIP; }
-  if (hipMalloc(&pl->d_board, sizeof(CoBoard)) != hipSuccess || hipMemset(pl->d_board, 0, sizeof(CoBoard)) != hipSuccess) { pool_free(pl); ctx->err = "work-area pool: no memory for the cooperation board"; return EH_E_NOMEM; }
+  if (pl->d_board.grow(1) != hipSuccess || hipMemset(pl->d_board, 0, sizeof(CoBoard)) != hipSuccess) { pool_free(pl); ctx->err = "work-area pool: no memory for the cooperation board"; return EH_E_NOMEM; }
   pl->refs = 1; g_pools.push_back(pl); ctx->pool = pl;
   return EH_OK;
 }
@@ -1485,18 +1503,11 @@ static int reserve(eh_ctx* ctx, uint64_t n, uint64_t in_bytes) {
   if (want_slots > n) want_slots = (uint32_t)(n ? n : 1);
   uint64_t stride = (SLOT_TABLE_BYTES + work_cap + 255) & ~255ull;
   if (!ctx->d_slots || ctx->nslots < want_slots || ctx->slot_cap != work_cap) {
-    if (ctx->d_slots) (void)hipFree(ctx->d_slots);
-    ctx->d_slots = nullptr;
-    HIPCHK(ctx, hipMalloc(&ctx->d_slots, stride * want_slots));
+    HIPCHK(ctx, ctx->d_slots.reset(stride * want_slots));
     ctx->nslots = want_slots; ctx->slot_cap = work_cap; ctx->slot_stride = stride;
   }
   uint64_t want_out = ctx->out_capacity_opt ? ctx->out_capacity_opt : (8 * (in_bytes ? in_bytes : ctx->corpus_bytes) + (2048ull << 20));
-  if (!ctx->d_out || ctx->out_cap < want_out) {
-    if (ctx->d_out) (void)hipFree(ctx->d_out);
-    ctx->d_out = nullptr;
-    HIPCHK(ctx, hipMalloc(&ctx->d_out, want_out));
-    ctx->out_cap = want_out;
-  }
+  HIPCHK(ctx, ctx->d_out.grow(want_out));
   return EH_OK;
 }
 
@@ -1510,19 +1521,21 @@ static int launch(eh_ctx* ctx, int mode, const int64_t seed[3], uint64_t first_c
   if (!ctx->h_coff.empty()) in_bytes = ctx->h_coff[corpus_first + n] - ctx->h_coff[corpus_first];
   int rc = reserve(ctx, n, in_bytes);
   if (rc) return rc;
-  if (!ctx->d_counters) { HIPCHK(ctx, hipMalloc(&ctx->d_counters, 4096)); HIPCHK(ctx, hipMalloc(&ctx->d_run, sizeof(RunState))); HIPCHK(ctx, hipMalloc(&ctx->d_params, sizeof(KParams))); }
+  HIPCHK(ctx, ctx->d_counters.grow(512));
+  HIPCHK(ctx, ctx->d_run.grow(1));
+  HIPCHK(ctx, ctx->d_params.grow(1));
   if (!ctx->h_sum) { HIPCHK(ctx, hipHostMalloc((void**)&ctx->h_sum, 128, hipHostMallocDefault)); memset(ctx->h_sum, 0, 128); }
 
   KParams p;
   memset(&p, 0, sizeof(p));
   p.corpus = dp(ctx->d_corpus); p.coff = dp(ctx->d_coff); p.corpus_first = corpus_first; p.n_paths = ctx->n_corpus; p.n = n; p.first_case = first_case;
-  p.mode = mode; p.run = dp(ctx->d_run); p.seeds = dp(ctx->d_seeds); p.cfg = ctx->cfg;
+  p.mode = mode; p.run = dp(ctx->d_run); p.seeds = dp(seeds_of(ctx)); p.cfg = ctx->cfg;
   if (profiled) { p.profiles = dp(ctx->d_profiles); p.profile_id = dp(profile_ids_of(ctx)); }   // (memset above: nullptr otherwise)
   const DevPool* pl = ctx->pool;
   p.work_cap = pl->work_cap;
   p.work_budget = ctx->work_budget;                                            // 0 = no budget (the default)
   p.fuse_stream_min = ctx->fuse_stream_min;
-  p.out = dp(ctx->d_out); p.out_cap = ctx->out_cap; p.out_cursor = dp(ctx->d_counters + 1);
+  p.out = dp(ctx->d_out); p.out_cap = ctx->d_out.cap; p.out_cursor = dp(ctx->d_counters + 1);
   p.out_off = dp(ctx->d_off); p.out_len = dp(ctx->d_len); p.status = dp(ctx->d_status); p.draws = dp(ctx->d_draws); p.lastm = dp(ctx->d_lastm); p.cycles = dp(ctx->d_cycles); p.peak = dp(ctx->d_peak); p.trace_off = dp(ctx->d_toff); p.trace_len = dp(ctx->d_tlen); p.flags = ctx->flags;
   p.ticket = dp(ctx->d_counters); p.in_bytes = dp(ctx->d_counters + 2); p.prof = dp(ctx->d_counters + 8);   // counters [8, 264) = prof
   p.slot_base = dp(ctx->d_slots); p.slot_stride = ctx->slot_stride;
@@ -1547,25 +1560,14 @@ static int launch(eh_ctx* ctx, int mode, const int64_t seed[3], uint64_t first_c
   if ((ctx->flags & EH_FLAG_ORDERED_OUTPUT) && n > 0) {
     // second arena + ordered offsets, then scan + gather on the same stream; the arenas swap roles so that
     // eh_result_device / eh_result_download see one contiguous case-ordered buffer
-    if (!ctx->d_out2 || ctx->out2_cap < ctx->out_cap) {
-      if (ctx->d_out2) (void)hipFree(ctx->d_out2);
-      ctx->d_out2 = nullptr;
-      HIPCHK(ctx, hipMalloc(&ctx->d_out2, ctx->out_cap));
-      ctx->out2_cap = ctx->out_cap;
-    }
-    if (!ctx->d_ord || ctx->ord_cap < n + 1) {
-      if (ctx->d_ord) (void)hipFree(ctx->d_ord);
-      ctx->d_ord = nullptr;
-      HIPCHK(ctx, hipMalloc(&ctx->d_ord, (n + 1) * 8));
-      ctx->ord_cap = n + 1;
-    }
+    HIPCHK(ctx, ctx->d_out2.grow(ctx->d_out.cap));
+    HIPCHK(ctx, ctx->d_ord.grow(n + 1));
     hipLaunchKernelGGL(eh_order_scan_kernel, dim3(1), dim3(64), 0, st, ctx->d_len, ctx->d_ord, n);
     uint32_t g = (uint32_t)ctx->cus * 32u; if (g > n) g = (uint32_t)n;
     hipLaunchKernelGGL(eh_order_gather_kernel, dim3(g), dim3(64), 0, st, ctx->d_out, ctx->d_out2, ctx->d_off, ctx->d_len, ctx->d_ord, n, 0ull);
     HIPCHK(ctx, hipMemcpyAsync(ctx->d_off, ctx->d_ord, n * 8, hipMemcpyDeviceToDevice, st));
     HIPCHK(ctx, hipGetLastError());
-    uint8_t* t = ctx->d_out; ctx->d_out = ctx->d_out2; ctx->d_out2 = t;
-    uint64_t tc = ctx->out_cap; ctx->out_cap = ctx->out2_cap; ctx->out2_cap = tc;
+    ctx->d_out.swap(ctx->d_out2);
     ctx->ordered = true;
   }
   ctx->last_stream = st; ctx->last_n = n; ctx->last_in_bytes = in_bytes; ctx->have_result = true;
@@ -1660,23 +1662,15 @@ void eh_destroy(eh_ctx* ctx) {
   (void)hipSetDevice(ctx->device);
   (void)hipDeviceSynchronize();
   if (ctx->comm) { ehcomm::Api* a = ehcomm::api(); if (a->h) (void)a->CommDestroy(ctx->comm); ctx->comm = nullptr; }
-  if (ctx->own_corpus) { (void)hipFree(ctx->d_corpus); (void)hipFree(ctx->d_coff); }
   pool_release(ctx);
-  (void)hipFree(ctx->d_slots); (void)hipFree(ctx->d_out); (void)hipFree(ctx->d_off); (void)hipFree(ctx->d_len);
-  (void)hipFree(ctx->d_status); (void)hipFree(ctx->d_draws); (void)hipFree(ctx->d_lastm); (void)hipFree(ctx->d_cycles); (void)hipFree(ctx->d_peak); (void)hipFree(ctx->d_toff); (void)hipFree(ctx->d_tlen); (void)hipFree(ctx->d_counters); if (ctx->h_sum) (void)hipHostFree(ctx->h_sum);
-  (void)hipFree(ctx->d_run); (void)hipFree(ctx->d_seeds); (void)hipFree(ctx->d_profiles);
-  for (int k = 0; k < 2; k++) { if (ctx->d_bounce[k]) (void)hipFree(ctx->d_bounce[k]); if (ctx->ev_g[k]) (void)hipEventDestroy(ctx->ev_g[k]); if (ctx->ev_c[k]) (void)hipEventDestroy(ctx->ev_c[k]); }
+  if (ctx->h_sum) (void)hipHostFree(ctx->h_sum);
+  for (int k = 0; k < 2; k++) { if (ctx->ev_g[k]) (void)hipEventDestroy(ctx->ev_g[k]); if (ctx->ev_c[k]) (void)hipEventDestroy(ctx->ev_c[k]); }
   if (ctx->dl_gather) (void)hipStreamDestroy(ctx->dl_gather);
   if (ctx->dl_copy) (void)hipStreamDestroy(ctx->dl_copy);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
-  if (ctx->d_params) (void)hipFree(ctx->d_params);
-  if (ctx->d_out2) (void)hipFree(ctx->d_out2);
-  if (ctx->d_ord) (void)hipFree(ctx->d_ord);
-  (void)hipFree(ctx->d_uq_digest); (void)hipFree(ctx->d_uq_first); (void)hipFree(ctx->d_uq_pfirst); (void)hipFree(ctx->d_uq_flag);
-  (void)hipFree(ctx->d_uq_term); (void)hipFree(ctx->d_uq_tab); (void)hipFree(ctx->d_sel);
   if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
   if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
-  delete ctx;
+  delete ctx;                                          // (the device buffers go with their owners: after the synchronise above)
 }
 
 static int co_collect(eh_ctx* ctx);
@@ -1747,10 +1741,10 @@ int eh_configure(eh_ctx* ctx, const eh_options* o) {
   return EH_OK;
 }
 
-static int set_corpus(eh_ctx* ctx, uint8_t* d, uint64_t* doff, bool own, uint64_t n, uint64_t nbytes) {
-  if (ctx->own_corpus) { (void)hipFree(ctx->d_corpus); (void)hipFree(ctx->d_coff); }
-  ctx->d_corpus = d; ctx->d_coff = doff; ctx->own_corpus = own; ctx->n_corpus = n; ctx->corpus_bytes = nbytes;
-  return EH_OK;
+// The corpus becomes the filled buffers (d, doff); what the context owned before goes with them when the caller returns.
+static void adopt_corpus(eh_ctx* ctx, DevBuf<uint8_t>& d, DevBuf<uint64_t>& doff, uint64_t n, uint64_t nbytes) {
+  ctx->own_corpus.swap(d); ctx->own_coff.swap(doff);
+  ctx->d_corpus = ctx->own_corpus; ctx->d_coff = ctx->own_coff; ctx->n_corpus = n; ctx->corpus_bytes = nbytes;
 }
 int eh_corpus_upload(eh_ctx* ctx, const uint8_t* data, const uint64_t* off, uint64_t n) {
   if (!ctx || !off || (!data && off[n] > 0)) return EH_E_INVALID;
@@ -1758,24 +1752,22 @@ int eh_corpus_upload(eh_ctx* ctx, const uint8_t* data, const uint64_t* off, uint
   HIPCHK(ctx, hipSetDevice(ctx->device));
   uint64_t nbytes = off[n];
   HIPCHK(ctx, hipDeviceSynchronize());                       // no launch may still read the previous corpus
-  if (ctx->own_corpus && ctx->own_corpus_cap >= nbytes && ctx->own_coff_cap >= n + 1) {      // steady state of a service: no hipMalloc / hipFree
+  if (ctx->own_corpus.cap >= nbytes && ctx->own_coff.cap >= n + 1) {      // steady state of a service: no hipMalloc / hipFree (an attached corpus: nothing is owned)
     if (nbytes) HIPCHK(ctx, hipMemcpy(ctx->d_corpus, data, nbytes, hipMemcpyHostToDevice));
     HIPCHK(ctx, hipMemcpy(ctx->d_coff, off, (n + 1) * 8, hipMemcpyHostToDevice));
     ctx->h_coff.assign(off, off + n + 1);
     ctx->n_corpus = n; ctx->corpus_bytes = nbytes;
     return EH_OK;
   }
-  uint8_t* d = nullptr; uint64_t* doff = nullptr;
-  uint64_t cap_b = nbytes + nbytes / 2 + 4096, cap_o = n + n / 2 + 16;                         // room to grow
-  hipError_t e = hipMalloc(&d, cap_b);
-  if (e == hipSuccess) e = hipMalloc(&doff, cap_o * 8);
+  DevBuf<uint8_t> d; DevBuf<uint64_t> doff;                  // (the corpus in use stays until the new one is complete)
+  hipError_t e = d.grow(nbytes + nbytes / 2 + 4096);         // room to grow
+  if (e == hipSuccess) e = doff.grow(n + n / 2 + 16);
   if (e == hipSuccess && nbytes) e = hipMemcpy(d, data, nbytes, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(doff, off, (n + 1) * 8, hipMemcpyHostToDevice);
-  if (e != hipSuccess) { if (d) (void)hipFree(d); if (doff) (void)hipFree(doff); HIPCHK(ctx, e); }
+  HIPCHK(ctx, e);
   ctx->h_coff.assign(off, off + n + 1);
-  int rc = set_corpus(ctx, d, doff, true, n, nbytes);
-  ctx->own_corpus_cap = cap_b; ctx->own_coff_cap = cap_o;
-  return rc;
+  adopt_corpus(ctx, d, doff, n, nbytes);
+  return EH_OK;
 }
 int eh_corpus_attach(eh_ctx* ctx, const void* d_data, const void* d_off, uint64_t n, uint64_t nbytes) {
   if (!ctx || !d_off) return EH_E_INVALID;
@@ -1784,7 +1776,9 @@ int eh_corpus_attach(eh_ctx* ctx, const void* d_data, const void* d_off, uint64_
   ctx->h_coff.resize(n + 1);
   HIPCHK(ctx, hipMemcpy(ctx->h_coff.data(), d_off, (n + 1) * 8, hipMemcpyDeviceToHost));
   if (ctx->h_coff[n] != nbytes) { ctx->err = "off[n] != nbytes"; return EH_E_INVALID; }
-  return set_corpus(ctx, (uint8_t*)d_data, (uint64_t*)d_off, false, n, nbytes);
+  ctx->own_corpus.release(); ctx->own_coff.release();
+  ctx->d_corpus = (uint8_t*)d_data; ctx->d_coff = (uint64_t*)d_off; ctx->n_corpus = n; ctx->corpus_bytes = nbytes;
+  return EH_OK;
 }
 
 // ---- multi-GPU: the arena over RCCL (eh_comm.h) ------------------------------------------------------------------------------
@@ -1794,22 +1788,17 @@ int eh_corpus_attach(eh_ctx* ctx, const void* d_data, const void* d_off, uint64_
     if (r_ != 0) { (ctx)->err = std::string(#call) + ": " + ((a)->GetErrorString ? (a)->GetErrorString(r_) : "RCCL error"); return EH_E_HIP; } \
   } while (0)
 
-// a device temporary of the collectives below: freed on every way out of the function
-struct DevTmp { void* p = nullptr; ~DevTmp() { if (p) (void)hipFree(p); } };
-
 // an owned corpus buffer for n entries / nbytes bytes (contents undefined); keeps the one it has when that is large enough
 static int corpus_own_buffers(eh_ctx* ctx, uint64_t n, uint64_t nbytes) {
   HIPCHK(ctx, hipSetDevice(ctx->device));
   HIPCHK(ctx, hipDeviceSynchronize());                       // no launch may still read the previous corpus
-  if (ctx->own_corpus && ctx->own_corpus_cap >= nbytes && ctx->own_coff_cap >= n + 1) { ctx->n_corpus = n; ctx->corpus_bytes = nbytes; return EH_OK; }
-  uint8_t* d = nullptr; uint64_t* doff = nullptr;
-  const uint64_t cap_b = nbytes + 4096, cap_o = n + 16;
-  hipError_t e = hipMalloc(&d, cap_b);
-  if (e == hipSuccess) e = hipMalloc(&doff, cap_o * 8);
-  if (e != hipSuccess) { if (d) (void)hipFree(d); if (doff) (void)hipFree(doff); HIPCHK(ctx, e); }
-  int rc = set_corpus(ctx, d, doff, true, n, nbytes);
-  ctx->own_corpus_cap = cap_b; ctx->own_coff_cap = cap_o;
-  return rc;
+  if (ctx->own_corpus.cap >= nbytes && ctx->own_coff.cap >= n + 1) { ctx->n_corpus = n; ctx->corpus_bytes = nbytes; return EH_OK; }
+  DevBuf<uint8_t> d; DevBuf<uint64_t> doff;
+  hipError_t e = d.grow(nbytes + 4096);
+  if (e == hipSuccess) e = doff.grow(n + 16);
+  HIPCHK(ctx, e);
+  adopt_corpus(ctx, d, doff, n, nbytes);
+  return EH_OK;
 }
 
 int eh_device_count(void) { int n = 0; return hipGetDeviceCount(&n) == hipSuccess && n > 0 ? n : 0; }
@@ -1868,9 +1857,8 @@ int eh_corpus_broadcast(eh_ctx* ctx, int root, const uint8_t* data, const uint64
   HIPCHK(ctx, hipSetDevice(ctx->device));
   void* stv = nullptr; int rc = eh_stream(ctx, &stv); if (rc) return rc;
   hipStream_t st = (hipStream_t)stv;
-  DevTmp hdr_mem;
-  HIPCHK(ctx, hipMalloc(&hdr_mem.p, 16));
-  uint64_t* d_hdr = (uint64_t*)hdr_mem.p;
+  DevBuf<uint64_t> d_hdr;
+  HIPCHK(ctx, d_hdr.grow(2));
   uint64_t hdr[2] = {is_root ? n : 0, is_root ? off[n] : 0};
   if (is_root) HIPCHK(ctx, hipMemcpy(d_hdr, hdr, 16, hipMemcpyHostToDevice));
   NCCLCHK(ctx, a, a->Broadcast(d_hdr, d_hdr, 2, ehcomm::kUint64, root, ctx->comm, st));
@@ -1909,9 +1897,8 @@ int eh_corpus_allgather(eh_ctx* ctx, const uint8_t* data, const uint64_t* off, u
   const int R = ctx->comm_n, me = ctx->comm_rank;
   const uint64_t B = off[n_local];
   // do all ranks bring the same shape?
-  DevTmp sz_mem;
-  HIPCHK(ctx, hipMalloc(&sz_mem.p, 16 * (size_t)R));
-  uint64_t* d_sz = (uint64_t*)sz_mem.p;
+  DevBuf<uint64_t> d_sz;
+  HIPCHK(ctx, d_sz.grow(2 * (uint64_t)R));
   uint64_t mine[2] = {n_local, B};
   HIPCHK(ctx, hipMemcpy(d_sz + 2 * me, mine, 16, hipMemcpyHostToDevice));
   NCCLCHK(ctx, a, a->AllGather(d_sz + 2 * me, d_sz, 2, ehcomm::kUint64, ctx->comm, st));
@@ -1998,7 +1985,7 @@ static int fuzz_calls(eh_ctx* ctx, const int64_t* seeds, const uint32_t* profile
   int rc = ensure_seeds(ctx, n);
   if (rc) return rc;
   // synchronous copies: the caller's arrays may be freed or reused as soon as this call returns
-  if (n) { HIPCHK(ctx, hipStreamSynchronize((hipStream_t)stream)); HIPCHK(ctx, hipMemcpy(ctx->d_seeds, seeds, n * 24, hipMemcpyHostToDevice)); }
+  if (n) { HIPCHK(ctx, hipStreamSynchronize((hipStream_t)stream)); HIPCHK(ctx, hipMemcpy(seeds_of(ctx), seeds, n * 24, hipMemcpyHostToDevice)); }
   if (profile && n) {
     HIPCHK(ctx, hipMemcpy(profile_ids_of(ctx), profile, n * 4, hipMemcpyHostToDevice));
     // profiles added since the last profiled launch.  The context's previous batch on this stream has ended (the wait above), and
@@ -2202,10 +2189,28 @@ int eh_host_alloc(void** p, uint64_t bytes) {
 }
 void eh_host_free(void* p) { if (p) (void)hipHostFree(p); }
 
+// what the calls that read the last batch's results begin with: there is one, and it has ended
+static int result_ready(eh_ctx* ctx) {
+  if (!ctx->have_result) { ctx->err = "no batch has run"; return EH_E_STATE; }
+  return eh_sync(ctx);
+}
+// The last batch's arena offsets and lengths on the host (n entries each), and the lengths' prefix sums: where each case starts in a
+// case-ordered copy (n + 1 entries).  `off` and `ord` may be NULL.
+static int result_off_len(eh_ctx* ctx, std::vector<uint64_t>* off, std::vector<uint64_t>& len, std::vector<uint64_t>* ord) {
+  const uint64_t n = ctx->last_n;
+  len.resize(n);
+  if (off) off->resize(n);
+  if (off && n) HIPCHK(ctx, hipMemcpy(off->data(), ctx->d_off, n * 8, hipMemcpyDeviceToHost));
+  if (n) HIPCHK(ctx, hipMemcpy(len.data(), ctx->d_len, n * 8, hipMemcpyDeviceToHost));
+  if (ord) {
+    ord->assign(n + 1, 0);
+    for (uint64_t i = 0; i < n; i++) (*ord)[i + 1] = (*ord)[i] + len[i];
+  }
+  return EH_OK;
+}
 int eh_result_device(eh_ctx* ctx, const uint8_t** d_data, const uint64_t** d_off, const uint64_t** d_len, const int32_t** d_status, uint64_t* total) {
   if (!ctx) return EH_E_INVALID;
-  if (!ctx->have_result) { ctx->err = "no batch has run"; return EH_E_STATE; }
-  int rc = eh_sync(ctx); if (rc) return rc;
+  int rc = result_ready(ctx); if (rc) return rc;
   if (d_data) *d_data = ctx->d_out;
   if (d_off) *d_off = ctx->d_off;
   if (d_len) *d_len = ctx->d_len;
@@ -2214,23 +2219,20 @@ int eh_result_device(eh_ctx* ctx, const uint8_t** d_data, const uint64_t** d_off
     unsigned long long cur = 0;
     if (ctx->ordered) HIPCHK(ctx, hipMemcpy(&cur, ctx->d_ord + ctx->last_n, 8, hipMemcpyDeviceToHost));   // bytes of the compact, case-ordered buffer
     else HIPCHK(ctx, hipMemcpy(&cur, ctx->d_counters + 1, 8, hipMemcpyDeviceToHost));                     // bump cursor of the completion-ordered arena (16-byte granules)
-    *total = cur > ctx->out_cap ? ctx->out_cap : cur;               // the cursor runs past the arena after EH_CASE_ARENA_FULL
+    *total = cur > ctx->d_out.cap ? ctx->d_out.cap : cur;               // the cursor runs past the arena after EH_CASE_ARENA_FULL
   }
   return EH_OK;
 }
 int eh_result_totals(eh_ctx* ctx, uint64_t* in_bytes, uint64_t* out_bytes, uint64_t* n_cases) {
   if (!ctx) return EH_E_INVALID;
-  if (!ctx->have_result) { ctx->err = "no batch has run"; return EH_E_STATE; }
-  int rc = eh_sync(ctx); if (rc) return rc;
-  uint64_t n = ctx->last_n;
+  int rc = result_ready(ctx); if (rc) return rc;
   if (out_bytes) {
-    std::vector<uint64_t> len(n ? n : 1);
-    if (n) HIPCHK(ctx, hipMemcpy(len.data(), ctx->d_len, n * 8, hipMemcpyDeviceToHost));
-    uint64_t s = 0; for (uint64_t i = 0; i < n; i++) s += len[i];
-    *out_bytes = s;
+    std::vector<uint64_t> len, ord;
+    rc = result_off_len(ctx, nullptr, len, &ord); if (rc) return rc;
+    *out_bytes = ord.back();
   }
   if (in_bytes) *in_bytes = ctx->last_in_bytes;
-  if (n_cases) *n_cases = n;
+  if (n_cases) *n_cases = ctx->last_n;
   return EH_OK;
 }
 // out[0] input bytes, out[1] output bytes, out[2] cases, out[3 + s] cases that ended with status s (0..5) - summed by the kernel,
@@ -2267,28 +2269,30 @@ static int gather_download(eh_ctx* ctx, uint8_t* data, uint64_t n, const uint64_
   uint64_t want = maxlen > chunk ? maxlen : chunk;
   if (want > total) want = total;
   want = (want + 4095) & ~4095ull;
-  if (!ctx->dl_gather) {
-    HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->dl_gather, hipStreamNonBlocking));
-    HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->dl_copy, hipStreamNonBlocking));
-    for (int k = 0; k < 2; k++) { HIPCHK(ctx, hipEventCreate(&ctx->ev_g[k])); HIPCHK(ctx, hipEventCreate(&ctx->ev_c[k])); }
+  // (each handle is made once, whichever of them an earlier call got as far as; a stream handle may be NULL where streams are not real)
+  if (!ctx->dl_gather) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->dl_gather, hipStreamNonBlocking));
+  if (!ctx->dl_copy) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->dl_copy, hipStreamNonBlocking));
+  for (int k = 0; k < 2; k++) {
+    if (!ctx->ev_g[k]) HIPCHK(ctx, hipEventCreate(&ctx->ev_g[k]));
+    if (!ctx->ev_c[k]) HIPCHK(ctx, hipEventCreate(&ctx->ev_c[k]));
   }
-  if (ctx->bounce_cap < want || ctx->bounce_chunk != chunk) {
-    for (int k = 0; k < 2; k++) { if (ctx->d_bounce[k]) (void)hipFree(ctx->d_bounce[k]); ctx->d_bounce[k] = nullptr; }
-    ctx->bounce_cap = 0;
-    for (int k = 0; k < 2; k++) HIPCHK(ctx, hipMalloc(&ctx->d_bounce[k], want));
-    ctx->bounce_cap = want; ctx->bounce_chunk = chunk;
+  if (ctx->d_bounce[0].cap < want || ctx->d_bounce[1].cap < want || ctx->bounce_chunk != chunk) {
+    ctx->d_bounce[0].release(); ctx->d_bounce[1].release();         // both go before either comes back: the new pair may need their room
+    for (int k = 0; k < 2; k++) HIPCHK(ctx, ctx->d_bounce[k].reset(want));
+    ctx->bounce_chunk = chunk;
   }
+  const uint64_t room = ctx->d_bounce[0].cap;                      // (of either buffer)
   uint64_t a = 0; int k = 0;
   while (a < n) {
     uint64_t b = a + 1;
-    while (b < n && ord[b + 1] - ord[a] <= ctx->bounce_cap) b++;
+    while (b < n && ord[b + 1] - ord[a] <= room) b++;
     const int buf = k & 1;
     if (k >= 2) HIPCHK(ctx, hipStreamWaitEvent(ctx->dl_gather, ctx->ev_c[buf], 0));     // the copy that last read this buffer
     uint64_t bytes = ord[b] - ord[a];
     if (bytes) {
       uint64_t cnt = b - a;
       uint32_t g = (uint32_t)ctx->cus * 32u; if (g > cnt) g = (uint32_t)cnt;
-      hipLaunchKernelGGL(eh_order_gather_kernel, dim3(g), dim3(64), 0, ctx->dl_gather, (const uint8_t*)ctx->d_out, ctx->d_bounce[buf],
+      hipLaunchKernelGGL(eh_order_gather_kernel, dim3(g), dim3(64), 0, ctx->dl_gather, (const uint8_t*)ctx->d_out, ctx->d_bounce[buf].p,
                          (const uint64_t*)(d_soff + a), (const uint64_t*)(d_slen + a), (const uint64_t*)(d_dst + a), cnt, ord[a]);
     }
     HIPCHK(ctx, hipEventRecord(ctx->ev_g[buf], ctx->dl_gather));
@@ -2303,14 +2307,13 @@ static int gather_download(eh_ctx* ctx, uint8_t* data, uint64_t n, const uint64_
 }
 int eh_result_download(eh_ctx* ctx, uint8_t* data, uint64_t cap, uint64_t* off, int32_t* status) {
   if (!ctx) return EH_E_INVALID;
-  if (!ctx->have_result) { ctx->err = "no batch has run"; return EH_E_STATE; }
-  int rc = eh_sync(ctx); if (rc) return rc;
-  uint64_t n = ctx->last_n;
-  std::vector<uint64_t> o(n ? n : 1), len(n ? n : 1);
-  if (n) { HIPCHK(ctx, hipMemcpy(o.data(), ctx->d_off, n * 8, hipMemcpyDeviceToHost)); HIPCHK(ctx, hipMemcpy(len.data(), ctx->d_len, n * 8, hipMemcpyDeviceToHost)); }
+  int rc = result_ready(ctx); if (rc) return rc;
+  const uint64_t n = ctx->last_n;
+  std::vector<uint64_t> o, len, ord;
+  rc = result_off_len(ctx, &o, len, &ord); if (rc) return rc;
   if (status && n) HIPCHK(ctx, hipMemcpy(status, ctx->d_status, n * 4, hipMemcpyDeviceToHost));
-  uint64_t total = 0; for (uint64_t i = 0; i < n; i++) total += len[i];
-  if (off) { uint64_t p = 0; for (uint64_t i = 0; i < n; i++) { off[i] = p; p += len[i]; } off[n] = p; }
+  const uint64_t total = ord[n];
+  if (off) memcpy(off, ord.data(), (n + 1) * 8);
   if (data) {
     if (total > cap) { ctx->err = "download buffer too small"; return EH_E_INVALID; }
     if (ctx->ordered) {                                          // already in case order and contiguous: one copy
@@ -2320,14 +2323,7 @@ int eh_result_download(eh_ctx* ctx, uint8_t* data, uint64_t cap, uint64_t* off, 
     // completion-ordered arena -> case order (gather_download)
     if (total == 0) return EH_OK;
     uint64_t maxlen = 0; for (uint64_t i = 0; i < n; i++) if (len[i] > maxlen) maxlen = len[i];
-    if (!ctx->d_ord || ctx->ord_cap < n + 1) {
-      if (ctx->d_ord) (void)hipFree(ctx->d_ord);
-      ctx->d_ord = nullptr;
-      HIPCHK(ctx, hipMalloc(&ctx->d_ord, (n + 1) * 8));
-      ctx->ord_cap = n + 1;
-    }
-    std::vector<uint64_t> ord(n + 1);
-    { uint64_t p = 0; for (uint64_t i = 0; i < n; i++) { ord[i] = p; p += len[i]; } ord[n] = p; }
+    HIPCHK(ctx, ctx->d_ord.grow(n + 1));
     HIPCHK(ctx, hipMemcpy(ctx->d_ord, ord.data(), (n + 1) * 8, hipMemcpyHostToDevice));
     return gather_download(ctx, data, n, ctx->d_off, ctx->d_len, ctx->d_ord, ord, maxlen);
   }
@@ -2394,8 +2390,7 @@ int eh_result_write_files(eh_ctx* ctx, const char* name_template, uint64_t first
 }
 int eh_result_fetch(eh_ctx* ctx, uint64_t i, uint8_t* buf, uint64_t cap, uint64_t* out_len) {
   if (!ctx || !out_len) return EH_E_INVALID;
-  if (!ctx->have_result) { ctx->err = "no batch has run"; return EH_E_STATE; }
-  int rc = eh_sync(ctx); if (rc) return rc;
+  int rc = result_ready(ctx); if (rc) return rc;
   if (i >= ctx->last_n) { ctx->err = "eh_result_fetch: case index outside the last batch"; return EH_E_INVALID; }
   uint64_t ol[2];
   HIPCHK(ctx, hipMemcpy(&ol[0], ctx->d_off + i, 8, hipMemcpyDeviceToHost));
@@ -2407,8 +2402,7 @@ int eh_result_fetch(eh_ctx* ctx, uint64_t i, uint8_t* buf, uint64_t cap, uint64_
 }
 int eh_result_diag(eh_ctx* ctx, uint64_t* draws, int32_t* last_mutator) {
   if (!ctx) return EH_E_INVALID;
-  if (!ctx->have_result) { ctx->err = "no batch has run"; return EH_E_STATE; }
-  int rc = eh_sync(ctx); if (rc) return rc;
+  int rc = result_ready(ctx); if (rc) return rc;
   uint64_t n = ctx->last_n;
   if (draws && n) HIPCHK(ctx, hipMemcpy(draws, ctx->d_draws, n * 8, hipMemcpyDeviceToHost));
   if (last_mutator && n) HIPCHK(ctx, hipMemcpy(last_mutator, ctx->d_lastm, n * 4, hipMemcpyDeviceToHost));
@@ -2416,8 +2410,7 @@ int eh_result_diag(eh_ctx* ctx, uint64_t* draws, int32_t* last_mutator) {
 }
 int eh_result_cycles(eh_ctx* ctx, uint64_t* cycles) {
   if (!ctx || !cycles) return EH_E_INVALID;
-  if (!ctx->have_result) { ctx->err = "no batch has run"; return EH_E_STATE; }
-  int rc = eh_sync(ctx); if (rc) return rc;
+  int rc = result_ready(ctx); if (rc) return rc;
   if (ctx->last_n) HIPCHK(ctx, hipMemcpy(cycles, ctx->d_cycles, ctx->last_n * 8, hipMemcpyDeviceToHost));
   return EH_OK;
 }
@@ -2439,15 +2432,13 @@ int eh_result_meta(eh_ctx* ctx, uint64_t i, uint8_t* buf, uint64_t cap, uint64_t
 }
 int eh_result_peak(eh_ctx* ctx, uint64_t* peak) {
   if (!ctx || !peak) return EH_E_INVALID;
-  if (!ctx->have_result) { ctx->err = "no batch has run"; return EH_E_STATE; }
-  int rc = eh_sync(ctx); if (rc) return rc;
+  int rc = result_ready(ctx); if (rc) return rc;
   if (ctx->last_n) HIPCHK(ctx, hipMemcpy(peak, ctx->d_peak, ctx->last_n * 8, hipMemcpyDeviceToHost));
   return EH_OK;
 }
 int eh_result_prof(eh_ctx* ctx, uint64_t* prof /* 256 values */) {
   if (!ctx || !prof) return EH_E_INVALID;
-  if (!ctx->have_result) { ctx->err = "no batch has run"; return EH_E_STATE; }
-  int rc = eh_sync(ctx); if (rc) return rc;
+  int rc = result_ready(ctx); if (rc) return rc;
   HIPCHK(ctx, hipMemcpy(prof, ctx->d_counters + 8, 256 * 8, hipMemcpyDeviceToHost));
   return EH_OK;
 }
@@ -2456,10 +2447,11 @@ int eh_result_prof(eh_ctx* ctx, uint64_t* prof /* 256 values */) {
 int eh_selftest_movers(eh_ctx* ctx, uint8_t* buf, uint64_t buf_len, const uint32_t* jobs, uint32_t njobs, uint32_t* eq_out) {
   if (!ctx || !buf || !jobs) return EH_E_INVALID;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  uint8_t* d = nullptr; uint32_t* dj = nullptr; uint32_t* de = nullptr;
-  hipError_t e = hipMalloc(&d, buf_len);
-  if (e == hipSuccess) e = hipMalloc(&dj, njobs * 20);
-  if (e == hipSuccess) e = hipMalloc(&de, njobs * 4);
+  DevBuf<uint8_t> d_buf; DevBuf<uint32_t> d_jobs, d_eq;
+  hipError_t e = d_buf.grow(buf_len);
+  if (e == hipSuccess) e = d_jobs.grow(5 * (uint64_t)njobs);
+  if (e == hipSuccess) e = d_eq.grow(njobs);
+  uint8_t* d = d_buf; uint32_t* dj = d_jobs; uint32_t* de = d_eq;
   if (e == hipSuccess) e = hipMemcpy(d, buf, buf_len, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(dj, jobs, njobs * 20, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemset(de, 0, njobs * 4);
@@ -2469,9 +2461,6 @@ int eh_selftest_movers(eh_ctx* ctx, uint8_t* buf, uint64_t buf_len, const uint32
   }
   if (e == hipSuccess) e = hipMemcpy(buf, d, buf_len, hipMemcpyDeviceToHost);
   if (e == hipSuccess && eq_out) e = hipMemcpy(eq_out, de, njobs * 4, hipMemcpyDeviceToHost);
-  if (d) (void)hipFree(d);
-  if (dj) (void)hipFree(dj);
-  if (de) (void)hipFree(de);
   HIPCHK(ctx, e);
   return EH_OK;
 }
@@ -2480,11 +2469,12 @@ int eh_selftest_movers(eh_ctx* ctx, uint8_t* buf, uint64_t buf_len, const uint32
 int eh_selftest_zlib(eh_ctx* ctx, int op, const uint8_t* in, uint64_t n, uint8_t* out, uint64_t cap, uint64_t* out_len, int32_t* ok) {
   if (!ctx || (!in && n) || !out || !out_len || !ok || op < 0 || op > 5 || op == 3 || (op <= 2 && cap < 64)) return EH_E_INVALID;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  uint8_t* di = nullptr; uint8_t* dout = nullptr; uint8_t* ds = nullptr; uint64_t* dr = nullptr;
-  hipError_t e = hipMalloc(&di, n + 16);
-  if (e == hipSuccess) e = hipMalloc(&dout, cap + 16);
-  if (e == hipSuccess) e = hipMalloc(&ds, sizeof(ZDef) > sizeof(ZInf) ? sizeof(ZDef) : sizeof(ZInf));
-  if (e == hipSuccess) e = hipMalloc(&dr, 16);
+  DevBuf<uint8_t> d_in, d_out, d_scratch; DevBuf<uint64_t> d_res;
+  hipError_t e = d_in.grow(n + 16);
+  if (e == hipSuccess) e = d_out.grow(cap + 16);
+  if (e == hipSuccess) e = d_scratch.grow(sizeof(ZDef) > sizeof(ZInf) ? sizeof(ZDef) : sizeof(ZInf));
+  if (e == hipSuccess) e = d_res.grow(2);
+  uint8_t* di = d_in; uint8_t* dout = d_out; uint8_t* ds = d_scratch; uint64_t* dr = d_res;
   if (e == hipSuccess && n) e = hipMemcpy(di, in, n, hipMemcpyHostToDevice);
   uint64_t r[2] = {0, 0};
   if (e == hipSuccess) {
@@ -2493,10 +2483,6 @@ int eh_selftest_zlib(eh_ctx* ctx, int op, const uint8_t* in, uint64_t n, uint8_t
   }
   if (e == hipSuccess) e = hipMemcpy(r, dr, 16, hipMemcpyDeviceToHost);
   if (e == hipSuccess && r[1] && r[0] <= cap && r[0]) e = hipMemcpy(out, dout, r[0], hipMemcpyDeviceToHost);
-  if (di) (void)hipFree(di);
-  if (dout) (void)hipFree(dout);
-  if (ds) (void)hipFree(ds);
-  if (dr) (void)hipFree(dr);
   HIPCHK(ctx, e);
   *out_len = r[0]; *ok = (int32_t)r[1];
   return EH_OK;
@@ -2531,7 +2517,7 @@ int eh_coop_stats(eh_ctx* ctx, uint64_t* out /* 8 values */) {
   if (!ctx || !out) return EH_E_INVALID;
   if (!ctx->pool) { ctx->err = "no work-area pool yet (eh_reserve or a first batch creates it)"; return EH_E_STATE; }
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  HIPCHK(ctx, hipMemcpy(out, (const uint8_t*)ctx->pool->d_board + offsetof(CoBoard, stat), 8 * 8, hipMemcpyDeviceToHost));
+  HIPCHK(ctx, hipMemcpy(out, (const uint8_t*)ctx->pool->d_board.p + offsetof(CoBoard, stat), 8 * 8, hipMemcpyDeviceToHost));
   return EH_OK;
 }
 // Has the last batch of this context finished (results ready, the context free for the next batch)?  Never blocks: what a host
@@ -2559,25 +2545,12 @@ static_assert(UQ_PIECE == EH_UNIQUE_PIECE_BYTES, "the header documents the piece
 static_assert(MAX_PROFILES == EH_MAX_PROFILES && sizeof(ProfileCfg) % 4 == 0, "the header documents the size of the profile table");
 // Device buffers for n cases and up to `pieces` pieces; they belong to the context and are reused while they fit.
 static int uq_ensure(eh_ctx* ctx, uint64_t n, uint64_t pieces, uint64_t slots) {
-  if (n > ctx->uq_case_cap) {
-    (void)hipFree(ctx->d_uq_digest); (void)hipFree(ctx->d_uq_first); (void)hipFree(ctx->d_uq_pfirst); (void)hipFree(ctx->d_uq_flag);
-    ctx->d_uq_digest = ctx->d_uq_first = ctx->d_uq_pfirst = nullptr; ctx->d_uq_flag = nullptr; ctx->uq_case_cap = 0;
-    HIPCHK(ctx, hipMalloc(&ctx->d_uq_digest, n * 8));
-    HIPCHK(ctx, hipMalloc(&ctx->d_uq_first, n * 8));
-    HIPCHK(ctx, hipMalloc(&ctx->d_uq_pfirst, (n + 1) * 8));
-    HIPCHK(ctx, hipMalloc(&ctx->d_uq_flag, n * 4));
-    ctx->uq_case_cap = n;
-  }
-  if (pieces > ctx->uq_term_cap) {
-    (void)hipFree(ctx->d_uq_term); ctx->d_uq_term = nullptr; ctx->uq_term_cap = 0;
-    HIPCHK(ctx, hipMalloc(&ctx->d_uq_term, pieces * 8));
-    ctx->uq_term_cap = pieces;
-  }
-  if (2 + 2 * slots > ctx->uq_tab_cap) {
-    (void)hipFree(ctx->d_uq_tab); ctx->d_uq_tab = nullptr; ctx->uq_tab_cap = 0;
-    HIPCHK(ctx, hipMalloc(&ctx->d_uq_tab, (2 + 2 * slots) * 8));
-    ctx->uq_tab_cap = 2 + 2 * slots;
-  }
+  HIPCHK(ctx, ctx->d_uq_digest.grow(n));
+  HIPCHK(ctx, ctx->d_uq_first.grow(n));
+  HIPCHK(ctx, ctx->d_uq_pfirst.grow(n + 1));
+  HIPCHK(ctx, ctx->d_uq_flag.grow(n));
+  HIPCHK(ctx, ctx->d_uq_term.grow(pieces));
+  HIPCHK(ctx, ctx->d_uq_tab.grow(2 + 2 * slots));
   return EH_OK;
 }
 static uint32_t uq_grid(const eh_ctx* ctx, uint64_t items) {
@@ -2618,7 +2591,7 @@ static int uq_result(eh_ctx* ctx, bool dedup) {
   dedup = dedup && ctx->uq_unique_seq != ctx->batch_seq;
   if (!digest && !dedup) return EH_OK;
   // every piece but a case's last is full: at most n + arena bytes / UQ_PIECE of them
-  const uint64_t arena = ctx->out_cap > ctx->out2_cap ? ctx->out_cap : ctx->out2_cap;
+  const uint64_t arena = ctx->d_out.cap > ctx->d_out2.cap ? ctx->d_out.cap : ctx->d_out2.cap;
   int rc = uq_launch(ctx, ctx->d_out, ctx->d_off, ctx->d_len, ctx->d_status, n, n + arena / UQ_PIECE + 1, digest, dedup, ctx->last_stream);
   if (rc) return rc;
   if (dedup) {
@@ -2652,8 +2625,8 @@ int eh_result_download_select(eh_ctx* ctx, const uint64_t* idx, uint64_t m, uint
   const uint64_t n = ctx->last_n;
   for (uint64_t k = 0; k < m; k++) if (idx[k] >= n) { ctx->err = "eh_result_download_select: case index outside the last batch"; return EH_E_INVALID; }
   int rc = eh_sync(ctx); if (rc) return rc;
-  std::vector<uint64_t> o(n ? n : 1), len(n ? n : 1);
-  if (n) { HIPCHK(ctx, hipMemcpy(o.data(), ctx->d_off, n * 8, hipMemcpyDeviceToHost)); HIPCHK(ctx, hipMemcpy(len.data(), ctx->d_len, n * 8, hipMemcpyDeviceToHost)); }
+  std::vector<uint64_t> o, len;
+  rc = result_off_len(ctx, &o, len, nullptr); if (rc) return rc;
   // the listed cases' offsets and lengths and where each goes, as the m-entry arrays the gather kernel reads: [0, m) offsets, [m, 2m) lengths, [2m, 3m] destinations
   std::vector<uint64_t> sel(3 * m + 1), ord(m + 1);
   uint64_t total = 0, maxlen = 0;
@@ -2663,11 +2636,7 @@ int eh_result_download_select(eh_ctx* ctx, const uint64_t* idx, uint64_t m, uint
   if (!data || !total) return EH_OK;                                 // (no buffer: off says what is needed)
   if (total > cap) { ctx->err = "eh_result_download_select: buffer too small"; return EH_E_INVALID; }
   for (uint64_t k = 0; k <= m; k++) sel[2 * m + k] = ord[k];
-  if (ctx->sel_cap < 3 * m + 1) {
-    (void)hipFree(ctx->d_sel); ctx->d_sel = nullptr; ctx->sel_cap = 0;
-    HIPCHK(ctx, hipMalloc(&ctx->d_sel, (3 * m + 1) * 8));
-    ctx->sel_cap = 3 * m + 1;
-  }
+  HIPCHK(ctx, ctx->d_sel.grow(3 * m + 1));
   HIPCHK(ctx, hipMemcpy(ctx->d_sel, sel.data(), (3 * m + 1) * 8, hipMemcpyHostToDevice));
   return gather_download(ctx, data, m, ctx->d_sel, ctx->d_sel + m, ctx->d_sel + 2 * m, ord, maxlen);
 }
@@ -2684,14 +2653,17 @@ int eh_selftest_unique(eh_ctx* ctx, const uint8_t* data, const uint64_t* off, co
   const uint64_t nbytes = off[n] - off[0];
   std::vector<uint64_t> len(n); uint64_t pieces = 0;
   for (uint64_t i = 0; i < n; i++) { len[i] = off[i + 1] - off[i]; pieces += (len[i] + UQ_PIECE - 1) / UQ_PIECE; }
-  DevTmp dd, dof, dl, ds;
-  HIPCHK(ctx, hipMalloc(&dd.p, nbytes ? nbytes : 1)); HIPCHK(ctx, hipMalloc(&dof.p, n * 8)); HIPCHK(ctx, hipMalloc(&dl.p, n * 8)); HIPCHK(ctx, hipMalloc(&ds.p, n * 4));
-  if (nbytes) HIPCHK(ctx, hipMemcpy(dd.p, data + off[0], nbytes, hipMemcpyHostToDevice));
+  DevBuf<uint8_t> dd; DevBuf<uint64_t> dof, dl; DevBuf<int32_t> ds;
+  HIPCHK(ctx, dd.grow(nbytes ? nbytes : 1));
+  HIPCHK(ctx, dof.grow(n));
+  HIPCHK(ctx, dl.grow(n));
+  HIPCHK(ctx, ds.grow(n));
+  if (nbytes) HIPCHK(ctx, hipMemcpy(dd, data + off[0], nbytes, hipMemcpyHostToDevice));
   std::vector<uint64_t> rel(n); for (uint64_t i = 0; i < n; i++) rel[i] = off[i] - off[0];
-  HIPCHK(ctx, hipMemcpy(dof.p, rel.data(), n * 8, hipMemcpyHostToDevice));
-  HIPCHK(ctx, hipMemcpy(dl.p, len.data(), n * 8, hipMemcpyHostToDevice));
-  HIPCHK(ctx, hipMemcpy(ds.p, status, n * 4, hipMemcpyHostToDevice));
-  int rc = uq_launch(ctx, (const uint8_t*)dd.p, (const uint64_t*)dof.p, (const uint64_t*)dl.p, (const int32_t*)ds.p, n, pieces, true, first_of != nullptr, nullptr);
+  HIPCHK(ctx, hipMemcpy(dof, rel.data(), n * 8, hipMemcpyHostToDevice));
+  HIPCHK(ctx, hipMemcpy(dl, len.data(), n * 8, hipMemcpyHostToDevice));
+  HIPCHK(ctx, hipMemcpy(ds, status, n * 4, hipMemcpyHostToDevice));
+  int rc = uq_launch(ctx, dd, dof, dl, ds, n, pieces, true, first_of != nullptr, nullptr);
   if (rc) return rc;
   HIPCHK(ctx, hipStreamSynchronize(nullptr));
   if (digest) HIPCHK(ctx, hipMemcpy(digest, ctx->d_uq_digest, n * 8, hipMemcpyDeviceToHost));
