@@ -41,6 +41,7 @@
 #include "eh_zip.h"
 #include "eh_unique.h"
 #include "eh_comm.h"
+#include "eh_coalesce.h"
 
 namespace eh {
 
@@ -1256,16 +1257,10 @@ struct eh_ctx {
   std::vector<ProfileCfg> profiles; std::unordered_map<std::string, uint32_t> profile_index;
   DevBuf<ProfileCfg> d_profiles; uint32_t profiles_on_device = 0;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  // request coalescing (eh_submit / eh_flush / eh_poll)
-  std::recursive_mutex co_lock;
-  std::condition_variable_any co_cv; bool co_collecting = false;   // a thread is waiting for / downloading the in-flight batch (lock released)
-  bool co_internal = false;                             // co_launch / co_collect are calling the batch entry points themselves
-  uint64_t co_next_ticket = 1, co_flush_cases = 4096, co_flush_bytes = 64ull << 20;
-  std::vector<uint8_t> co_data; std::vector<uint64_t> co_off{0}; std::vector<int64_t> co_seeds; std::vector<uint32_t> co_profile; std::vector<uint64_t> co_tickets;   // pending batch
-  bool co_inflight = false; std::vector<uint64_t> co_inflight_tickets;                  // launched, results still on the device
-  struct CoResult { std::vector<uint8_t> out; int32_t status; };
-  std::vector<uint64_t> co_cancelled;                                                   // in-flight tickets nobody will poll
-  std::map<uint64_t, CoResult> co_done;                                                 // downloaded, not polled yet
+  // request coalescing (eh_submit / eh_flush / eh_poll): the bookkeeping (eh_coalesce.h) and its lock, which a public entry point takes
+  // once and no function below it takes again
+  Coalescer co; std::mutex co_lock;
+  std::condition_variable co_cv; bool co_collecting = false;       // a thread is waiting for / downloading the in-flight batch (lock released)
   void* comm = nullptr; int comm_rank = 0, comm_n = 1;   // RCCL communicator of this context's device (eh_comm_init / eh_comm_init_local)
   hipStream_t last_stream = nullptr;
   hipStream_t own_stream = nullptr;                     // eh_stream: a stream of the context's own (non-blocking), made on first request
@@ -1289,13 +1284,13 @@ struct eh_ctx {
   } while (0)
 
 // A context that has coalesced requests pending or in flight (eh_submit .. eh_poll) belongs to the coalescer: a batch,
-// a corpus or a configuration from outside would overwrite the buffers and options those requests run with.
-#define CO_GUARD(ctx)                                                                                              \
-  std::lock_guard<std::recursive_mutex> co_guard_((ctx)->co_lock);                                                  \
-  if (!(ctx)->co_internal && ((ctx)->co_inflight || !(ctx)->co_tickets.empty())) {                                  \
-    (ctx)->err = "coalesced requests are pending on this context: eh_flush and eh_poll them first, or use a context of its own"; \
-    return EH_E_STATE;                                                                                              \
-  }
+// a corpus or a configuration from outside would overwrite the buffers and options those requests run with.  What those entry
+// points ask first, co_lock held (the coalescer itself calls the functions below them, which do not ask).
+static int co_idle(eh_ctx* ctx) {
+  if (!ctx->co.busy()) return EH_OK;
+  ctx->err = "coalesced requests are pending on this context: eh_flush and eh_poll them first, or use a context of its own";
+  return EH_E_STATE;
+}
 
 namespace {
 
@@ -1615,7 +1610,7 @@ const char* eh_last_error(eh_ctx* ctx) { return ctx ? ctx->err.c_str() : "null c
 uint64_t eh_last_error_copy(eh_ctx* ctx, char* buf, uint64_t cap) {
   if (!buf || !cap) return 0;
   if (!ctx) { buf[0] = 0; return 0; }
-  std::lock_guard<std::recursive_mutex> g(ctx->co_lock);            // the coalescer's calls set the text under this lock
+  std::lock_guard<std::mutex> g(ctx->co_lock);                      // the coalescer's calls set the text under this lock
   uint64_t n = ctx->err.size() < cap - 1 ? ctx->err.size() : cap - 1;
   memcpy(buf, ctx->err.data(), n); buf[n] = 0;
   return n;
@@ -1673,19 +1668,19 @@ void eh_destroy(eh_ctx* ctx) {
   delete ctx;                                          // (the device buffers go with their owners: after the synchronise above)
 }
 
-static int co_collect(eh_ctx* ctx);
+static int co_collect(eh_ctx* ctx, std::unique_lock<std::mutex>& lk);
 int eh_configure(eh_ctx* ctx, const eh_options* o) {
   if (!ctx || !o) return EH_E_INVALID;
   if (o->abi_version != EH_ABI_VERSION) { ctx->err = "eh_options.abi_version mismatch"; return EH_E_INVALID; }
   // Requests that are still PENDING run with the configuration in force when they are launched, so a new one is refused
   // (eh_flush them first).  A batch that is already in flight carries its configuration with it (launch() copies it into the
   // kernel's argument block) but owns the context's result buffers, which the next launch may re-size: it is collected first.
-  std::lock_guard<std::recursive_mutex> co_guard_(ctx->co_lock);
-  if (!ctx->co_internal && !ctx->co_tickets.empty()) {
+  std::unique_lock<std::mutex> lk(ctx->co_lock);
+  if (ctx->co.pending.size()) {
     ctx->err = "coalesced requests are pending on this context: eh_flush them first, or use a context of its own";
     return EH_E_STATE;
   }
-  if (!ctx->co_internal && ctx->co_inflight) { int rcc = co_collect(ctx); if (rcc) return rcc; }
+  if (ctx->co.in_flight) { int rcc = co_collect(ctx, lk); if (rcc) return rcc; }
   if (o->sequence_muta) {
     ctx->err = "sequence_muta (--consequtive-mutators, erlamsa_main.erl:223-235) chains the mutator scores from case to case: a batch of independent cases cannot keep that order; route this run to the BEAM path";
     return EH_E_UNSUPPORTED;
@@ -1746,9 +1741,7 @@ static void adopt_corpus(eh_ctx* ctx, DevBuf<uint8_t>& d, DevBuf<uint64_t>& doff
   ctx->own_corpus.swap(d); ctx->own_coff.swap(doff);
   ctx->d_corpus = ctx->own_corpus; ctx->d_coff = ctx->own_coff; ctx->n_corpus = n; ctx->corpus_bytes = nbytes;
 }
-int eh_corpus_upload(eh_ctx* ctx, const uint8_t* data, const uint64_t* off, uint64_t n) {
-  if (!ctx || !off || (!data && off[n] > 0)) return EH_E_INVALID;
-  CO_GUARD(ctx);
+static int corpus_upload(eh_ctx* ctx, const uint8_t* data, const uint64_t* off, uint64_t n) {   // co_lock held (eh_corpus_upload, co_launch)
   HIPCHK(ctx, hipSetDevice(ctx->device));
   uint64_t nbytes = off[n];
   HIPCHK(ctx, hipDeviceSynchronize());                       // no launch may still read the previous corpus
@@ -1769,9 +1762,14 @@ int eh_corpus_upload(eh_ctx* ctx, const uint8_t* data, const uint64_t* off, uint
   adopt_corpus(ctx, d, doff, n, nbytes);
   return EH_OK;
 }
+int eh_corpus_upload(eh_ctx* ctx, const uint8_t* data, const uint64_t* off, uint64_t n) {
+  if (!ctx || !off || (!data && off[n] > 0)) return EH_E_INVALID;
+  std::lock_guard<std::mutex> g(ctx->co_lock); if (int rc = co_idle(ctx)) return rc;
+  return corpus_upload(ctx, data, off, n);
+}
 int eh_corpus_attach(eh_ctx* ctx, const void* d_data, const void* d_off, uint64_t n, uint64_t nbytes) {
   if (!ctx || !d_off) return EH_E_INVALID;
-  CO_GUARD(ctx);
+  std::lock_guard<std::mutex> g(ctx->co_lock); if (int rc = co_idle(ctx)) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   ctx->h_coff.resize(n + 1);
   HIPCHK(ctx, hipMemcpy(ctx->h_coff.data(), d_off, (n + 1) * 8, hipMemcpyDeviceToHost));
@@ -1848,7 +1846,7 @@ int eh_comm_destroy(eh_ctx* ctx) {
 // the corpus as after eh_corpus_upload.  Three collectives on the context's stream: the sizes, the bytes, the offsets.
 int eh_corpus_broadcast(eh_ctx* ctx, int root, const uint8_t* data, const uint64_t* off, uint64_t n) {
   if (!ctx) return EH_E_INVALID;
-  CO_GUARD(ctx);
+  std::lock_guard<std::mutex> g(ctx->co_lock); if (int rc = co_idle(ctx)) return rc;
   if (!ctx->comm) { ctx->err = "eh_comm_init first"; return EH_E_STATE; }
   if (root < 0 || root >= ctx->comm_n) return EH_E_INVALID;
   const bool is_root = ctx->comm_rank == root;
@@ -1888,7 +1886,7 @@ int eh_corpus_broadcast(eh_ctx* ctx, int root, const uint8_t* data, const uint64
 // ncclAllGather fills in the others, so each xGMI link carries 1/nranks of the arena.
 int eh_corpus_allgather(eh_ctx* ctx, const uint8_t* data, const uint64_t* off, uint64_t n_local) {
   if (!ctx || !off || (!data && off[n_local] > 0)) return EH_E_INVALID;
-  CO_GUARD(ctx);
+  std::lock_guard<std::mutex> g(ctx->co_lock); if (int rc = co_idle(ctx)) return rc;
   if (!ctx->comm) { ctx->err = "eh_comm_init first"; return EH_E_STATE; }
   ehcomm::Api* a = ehcomm::api();
   HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -1963,19 +1961,18 @@ int eh_corpus_broadcast_local(eh_ctx** ctxs, int nctx, int root) {
 int eh_reserve(eh_ctx* ctx, uint64_t max_cases) {
   if (!ctx) return EH_E_INVALID;
   if (!ctx->configured || !ctx->d_corpus) { ctx->err = "configure and load a corpus first"; return EH_E_STATE; }
-  std::lock_guard<std::recursive_mutex> g(ctx->co_lock);
+  std::lock_guard<std::mutex> g(ctx->co_lock);
   int rc = reserve(ctx, max_cases, 0);
   return rc ? rc : ensure_seeds(ctx, max_cases);     // (per-call seeds and profile ids: eh_fuzz_calls / eh_fuzz_calls_profiled never allocate either)
 }
 
 int eh_fuzz_batch(eh_ctx* ctx, const int64_t seed[3], uint64_t first_case, uint64_t corpus_first, uint64_t n, void* stream) {
   if (!ctx || !seed) return EH_E_INVALID;
-  CO_GUARD(ctx);
+  std::lock_guard<std::mutex> g(ctx->co_lock); if (int rc = co_idle(ctx)) return rc;
   return launch(ctx, 0, seed, first_case, corpus_first, n, (hipStream_t)stream);
 }
+// co_lock held (fuzz_calls_idle, co_launch): per-case seeds, and profile ids where `profile` is not NULL
 static int fuzz_calls(eh_ctx* ctx, const int64_t* seeds, const uint32_t* profile, uint64_t corpus_first, uint64_t n, void* stream) {
-  if (!ctx || !seeds) return EH_E_INVALID;
-  CO_GUARD(ctx);
   if (profile) {
     if (!ctx->configured) { ctx->err = "configure first"; return EH_E_STATE; }
     const uint32_t count = (uint32_t)ctx->profiles.size();
@@ -1997,17 +1994,22 @@ static int fuzz_calls(eh_ctx* ctx, const int64_t* seeds, const uint32_t* profile
   int64_t dummy[3] = {0, 0, 0};
   return launch(ctx, 1, dummy, 1, corpus_first, n, (hipStream_t)stream, profile != nullptr && n > 0);
 }
+static int fuzz_calls_idle(eh_ctx* ctx, const int64_t* seeds, const uint32_t* profile, uint64_t corpus_first, uint64_t n, void* stream) {
+  if (!ctx || !seeds) return EH_E_INVALID;
+  std::lock_guard<std::mutex> g(ctx->co_lock); if (int rc = co_idle(ctx)) return rc;
+  return fuzz_calls(ctx, seeds, profile, corpus_first, n, stream);
+}
 int eh_fuzz_calls(eh_ctx* ctx, const int64_t* seeds, uint64_t corpus_first, uint64_t n, void* stream) {
-  return fuzz_calls(ctx, seeds, nullptr, corpus_first, n, stream);
+  return fuzz_calls_idle(ctx, seeds, nullptr, corpus_first, n, stream);
 }
 int eh_fuzz_calls_profiled(eh_ctx* ctx, const int64_t* seeds, const uint32_t* profile, uint64_t corpus_first, uint64_t n, void* stream) {
   if (!profile) return EH_E_INVALID;
-  return fuzz_calls(ctx, seeds, profile, corpus_first, n, stream);
+  return fuzz_calls_idle(ctx, seeds, profile, corpus_first, n, stream);
 }
 // ---- option profiles ----------------------------------------------------------------------------------------
 int eh_profile_add(eh_ctx* ctx, const char* mutations, const char* patterns, double blockscale, uint32_t* id) {
   if (!ctx || !id) return EH_E_INVALID;
-  std::lock_guard<std::recursive_mutex> g(ctx->co_lock);
+  std::lock_guard<std::mutex> g(ctx->co_lock);
   if (!ctx->configured) { ctx->err = "configure first"; return EH_E_STATE; }
   ProfileCfg pc;
   int rc = parse_profile(ctx, mutations, patterns, blockscale, pc);
@@ -2026,64 +2028,50 @@ int eh_profile_add(eh_ctx* ctx, const char* mutations, const char* patterns, dou
 }
 int eh_profile_count(eh_ctx* ctx, uint32_t* n) {
   if (!ctx || !n) return EH_E_INVALID;
-  std::lock_guard<std::recursive_mutex> g(ctx->co_lock);
+  std::lock_guard<std::mutex> g(ctx->co_lock);
   *n = (uint32_t)ctx->profiles.size();
   return EH_OK;
 }
 // ---- request coalescing -------------------------------------------------------------------------------------
+static int result_totals(eh_ctx* ctx, uint64_t* in_bytes, uint64_t* out_bytes, uint64_t* n_cases);
+static int result_download(eh_ctx* ctx, uint8_t* data, uint64_t cap, uint64_t* off, int32_t* status);
 // Brings the launched batch's results to the host (one download) and files them under their tickets.
-static int co_collect(eh_ctx* ctx) {
-  // (the caller holds co_lock exactly once.)  The wait for the batch and the download happen WITHOUT the lock, so that
-  // other threads keep submitting to the next batch meanwhile; a second collector waits for the first.
-  while (ctx->co_collecting) ctx->co_cv.wait(ctx->co_lock);
-  if (!ctx->co_inflight) return EH_OK;
+// `lk` is the caller's hold on co_lock: the wait for the batch and the download happen WITHOUT it, so that other threads keep
+// submitting to the next batch meanwhile; a second collector waits for the first.
+static int co_collect(eh_ctx* ctx, std::unique_lock<std::mutex>& lk) {
+  ctx->co_cv.wait(lk, [ctx] { return !ctx->co_collecting; });
+  if (!ctx->co.in_flight) return EH_OK;
   ctx->co_collecting = true;
-  const std::vector<uint64_t> tickets = ctx->co_inflight_tickets;
+  const std::vector<uint64_t> tickets = ctx->co.flying;
   const uint64_t n = tickets.size();
-  ctx->co_lock.unlock();
+  lk.unlock();
   uint64_t in_b = 0, out_b = 0, nc = 0;
   std::vector<uint8_t> data; std::vector<uint64_t> off(n + 1); std::vector<int32_t> st(n ? n : 1);
-  int rc = eh_result_totals(ctx, &in_b, &out_b, &nc);
+  int rc = result_totals(ctx, &in_b, &out_b, &nc);
   if (!rc && nc != n) { ctx->err = "coalescer: the context's last batch is not the one that was flushed"; rc = EH_E_STATE; }
-  if (!rc) { data.resize(out_b ? out_b : 1); rc = eh_result_download(ctx, data.data(), data.size(), off.data(), st.data()); }
-  ctx->co_lock.lock();
-  if (!rc) {
-    for (uint64_t i = 0; i < n; i++) {
-      bool dropped = false;
-      for (uint64_t t : ctx->co_cancelled) if (t == tickets[i]) dropped = true;
-      if (dropped) continue;
-      eh_ctx::CoResult r; r.out.assign(data.begin() + off[i], data.begin() + off[i + 1]); r.status = st[i];
-      ctx->co_done.emplace(tickets[i], std::move(r));
-    }
-    ctx->co_cancelled.clear();
-    ctx->co_inflight = false; ctx->co_inflight_tickets.clear();
-  }
-  ctx->co_collecting = false;
-  ctx->co_cv.notify_all();
+  if (!rc) { data.resize(out_b ? out_b : 1); rc = result_download(ctx, data.data(), data.size(), off.data(), st.data()); }
+  lk.lock();
+  if (!rc) ctx->co.collected(tickets, data.data(), off.data(), st.data());   // (a failed download: the batch stays in flight)
+  ctx->co_collecting = false; ctx->co_cv.notify_all();
   return rc;
 }
-// co_lock held.  Launches the pending batch (after collecting the previous one: one result buffer per context).
-static int co_launch(eh_ctx* ctx) {
-  if (ctx->co_tickets.empty()) return EH_OK;
-  int rc = co_collect(ctx);
+// Launches the pending batch (after collecting the previous one: one result buffer per context).
+static int co_launch(eh_ctx* ctx, std::unique_lock<std::mutex>& lk) {
+  if (!ctx->co.pending.size()) return EH_OK;
+  int rc = co_collect(ctx, lk);
   if (rc) return rc;
-  if (ctx->co_tickets.empty()) return EH_OK;                        // (co_collect lets other threads in: one of them has launched the batch)
-  const uint64_t n = ctx->co_tickets.size();
-  ctx->co_internal = true;
-  rc = eh_corpus_upload(ctx, ctx->co_data.data(), ctx->co_off.data(), n);
-  bool profiled = false;                                            // requests that all run under profile 0 take the unprofiled launch
-  for (uint32_t id : ctx->co_profile) profiled = profiled || id != 0;
-  if (!rc) rc = fuzz_calls(ctx, ctx->co_seeds.data(), profiled ? ctx->co_profile.data() : nullptr, 0, n, nullptr);
-  ctx->co_internal = false;
-  if (rc) return rc;
-  ctx->co_inflight = true; ctx->co_inflight_tickets.swap(ctx->co_tickets);
-  ctx->co_tickets.clear(); ctx->co_data.clear(); ctx->co_off.assign(1, 0); ctx->co_seeds.clear(); ctx->co_profile.clear();
-  return EH_OK;
+  const CoBatch& b = ctx->co.pending;
+  if (!b.size()) return EH_OK;                                      // (co_collect lets other threads in: one of them has launched the batch)
+  rc = corpus_upload(ctx, b.data.data(), b.off.data(), b.size());
+  // requests that all run under profile 0 take the unprofiled launch
+  if (!rc) rc = fuzz_calls(ctx, b.seeds.data(), b.profiled() ? b.profile.data() : nullptr, 0, b.size(), nullptr);
+  if (!rc) ctx->co.launched();
+  return rc;
 }
 int eh_coalesce_limits(eh_ctx* ctx, uint64_t flush_cases, uint64_t flush_bytes) {
   if (!ctx || !flush_cases || !flush_bytes) return EH_E_INVALID;
-  std::lock_guard<std::recursive_mutex> g(ctx->co_lock);
-  ctx->co_flush_cases = flush_cases; ctx->co_flush_bytes = flush_bytes;
+  std::lock_guard<std::mutex> g(ctx->co_lock);
+  ctx->co.flush_cases = flush_cases; ctx->co.flush_bytes = flush_bytes;
   return EH_OK;
 }
 int eh_submit(eh_ctx* ctx, const uint8_t* data, uint64_t len, const int64_t seed[3], uint64_t* ticket) {
@@ -2092,66 +2080,43 @@ int eh_submit(eh_ctx* ctx, const uint8_t* data, uint64_t len, const int64_t seed
 int eh_submit_profiled(eh_ctx* ctx, const uint8_t* data, uint64_t len, const int64_t seed[3], uint32_t profile, uint64_t* ticket) {
   if (!ctx || !seed || !ticket || (!data && len)) return EH_E_INVALID;
   if (!ctx->configured) { ctx->err = "configure first"; return EH_E_STATE; }
-  std::lock_guard<std::recursive_mutex> g(ctx->co_lock);
+  std::unique_lock<std::mutex> lk(ctx->co_lock);
   if (profile >= ctx->profiles.size()) { ctx->err = "no profile " + std::to_string(profile) + " (eh_profile_count = " + std::to_string(ctx->profiles.size()) + ")"; return EH_E_INVALID; }
-  const size_t d0 = ctx->co_data.size(), o0 = ctx->co_off.size(), s0 = ctx->co_seeds.size(), t0 = ctx->co_tickets.size(), p0 = ctx->co_profile.size();
-  const uint64_t mine = ctx->co_next_ticket;
-  try {
-    ctx->co_data.insert(ctx->co_data.end(), data, data + len);
-    ctx->co_off.push_back(ctx->co_data.size());
-    ctx->co_seeds.insert(ctx->co_seeds.end(), seed, seed + 3);
-    ctx->co_profile.push_back(profile);
-    ctx->co_tickets.push_back(mine);
-  } catch (const std::bad_alloc&) { ctx->co_data.resize(d0); ctx->co_off.resize(o0); ctx->co_seeds.resize(s0); ctx->co_profile.resize(p0); ctx->co_tickets.resize(t0); return EH_E_NOMEM; }
-  ctx->co_next_ticket++;                                  // (before any launch: co_collect lets other submitters in)
-  if (ctx->co_tickets.size() >= ctx->co_flush_cases || ctx->co_data.size() >= ctx->co_flush_bytes) {
-    int rc = co_launch(ctx);
+  const uint64_t mine = ctx->co.next_ticket;
+  if (!ctx->co.pending.push(mine, data, len, seed, profile)) return EH_E_NOMEM;
+  ctx->co.next_ticket++;                                  // (before any launch: co_collect lets other submitters in)
+  if (ctx->co.at_limit()) {
+    int rc = co_launch(ctx, lk);
     // a launch that fails takes this request back out (the caller gets no ticket for it); the others stay queued for the next flush
-    if (rc) { std::string why = ctx->err; (void)eh_cancel(ctx, mine); ctx->err = why; return rc; }
+    if (rc) { (void)ctx->co.cancel(mine); return rc; }
   }
   *ticket = mine;
   return EH_OK;
 }
 int eh_cancel(eh_ctx* ctx, uint64_t ticket) {
   if (!ctx) return EH_E_INVALID;
-  std::lock_guard<std::recursive_mutex> g(ctx->co_lock);
-  if (ctx->co_done.erase(ticket)) return EH_OK;
-  for (size_t i = 0; i < ctx->co_tickets.size(); i++) if (ctx->co_tickets[i] == ticket) {      // not launched yet: leaves the batch
-    const uint64_t a = ctx->co_off[i], b = ctx->co_off[i + 1];
-    ctx->co_data.erase(ctx->co_data.begin() + a, ctx->co_data.begin() + b);
-    ctx->co_off.erase(ctx->co_off.begin() + i + 1);
-    for (size_t k = i + 1; k < ctx->co_off.size(); k++) ctx->co_off[k] -= b - a;
-    ctx->co_seeds.erase(ctx->co_seeds.begin() + 3 * i, ctx->co_seeds.begin() + 3 * i + 3);
-    ctx->co_profile.erase(ctx->co_profile.begin() + i);
-    ctx->co_tickets.erase(ctx->co_tickets.begin() + i);
-    return EH_OK;
-  }
-  for (uint64_t t : ctx->co_inflight_tickets) if (t == ticket) { ctx->co_cancelled.push_back(ticket); return EH_OK; }   // dropped when the batch is collected
-  ctx->err = "unknown or already consumed ticket";
-  return EH_E_INVALID;
+  std::lock_guard<std::mutex> g(ctx->co_lock);
+  int rc = ctx->co.cancel(ticket);
+  if (rc) ctx->err = "unknown or already consumed ticket";
+  return rc;
 }
 int eh_flush(eh_ctx* ctx) {
   if (!ctx) return EH_E_INVALID;
-  std::lock_guard<std::recursive_mutex> g(ctx->co_lock);
-  return co_launch(ctx);
+  std::unique_lock<std::mutex> lk(ctx->co_lock);
+  return co_launch(ctx, lk);
 }
 int eh_poll(eh_ctx* ctx, uint64_t ticket, uint8_t* out, uint64_t cap, uint64_t* out_len, int32_t* status) {
   if (!ctx || !out_len || !status) return EH_E_INVALID;
-  std::lock_guard<std::recursive_mutex> g(ctx->co_lock);
-  auto it = ctx->co_done.find(ticket);
-  if (it == ctx->co_done.end()) {
-    for (uint64_t t : ctx->co_tickets) if (t == ticket) return EH_E_AGAIN;
-    bool launched = false;
-    for (uint64_t t : ctx->co_inflight_tickets) if (t == ticket) launched = true;
-    if (!launched) { ctx->err = "unknown or already consumed ticket"; return EH_E_INVALID; }
-    int rc = co_collect(ctx);                                       // waits for the batch
-    if (rc) return rc;
-    it = ctx->co_done.find(ticket);
-  }
+  std::unique_lock<std::mutex> lk(ctx->co_lock);
+  const CoWhere w = ctx->co.where(ticket);
+  if (w == CoWhere::pending) return EH_E_AGAIN;
+  if (w == CoWhere::unknown) { ctx->err = "unknown or already consumed ticket"; return EH_E_INVALID; }
+  if (w == CoWhere::in_flight) { int rc = co_collect(ctx, lk); if (rc) return rc; }   // waits for the batch
+  auto it = ctx->co.done.find(ticket);
   *out_len = it->second.out.size(); *status = it->second.status;
   if (it->second.out.size() > cap || (!out && !it->second.out.empty())) { ctx->err = "eh_poll: buffer too small"; return EH_E_INVALID; }
   if (!it->second.out.empty()) memcpy(out, it->second.out.data(), it->second.out.size());
-  ctx->co_done.erase(it);
+  ctx->co.done.erase(it);
   return EH_OK;
 }
 
@@ -2223,8 +2188,9 @@ int eh_result_device(eh_ctx* ctx, const uint8_t** d_data, const uint64_t** d_off
   }
   return EH_OK;
 }
-int eh_result_totals(eh_ctx* ctx, uint64_t* in_bytes, uint64_t* out_bytes, uint64_t* n_cases) {
-  if (!ctx) return EH_E_INVALID;
+int eh_result_totals(eh_ctx* ctx, uint64_t* in_bytes, uint64_t* out_bytes, uint64_t* n_cases) { return ctx ? result_totals(ctx, in_bytes, out_bytes, n_cases) : EH_E_INVALID; }
+// (no lock, here or in result_download: co_collect calls both after it has released co_lock)
+static int result_totals(eh_ctx* ctx, uint64_t* in_bytes, uint64_t* out_bytes, uint64_t* n_cases) {
   int rc = result_ready(ctx); if (rc) return rc;
   if (out_bytes) {
     std::vector<uint64_t> len, ord;
@@ -2305,8 +2271,8 @@ static int gather_download(eh_ctx* ctx, uint8_t* data, uint64_t n, const uint64_
   HIPCHK(ctx, hipGetLastError());
   return EH_OK;
 }
-int eh_result_download(eh_ctx* ctx, uint8_t* data, uint64_t cap, uint64_t* off, int32_t* status) {
-  if (!ctx) return EH_E_INVALID;
+int eh_result_download(eh_ctx* ctx, uint8_t* data, uint64_t cap, uint64_t* off, int32_t* status) { return ctx ? result_download(ctx, data, cap, off, status) : EH_E_INVALID; }
+static int result_download(eh_ctx* ctx, uint8_t* data, uint64_t cap, uint64_t* off, int32_t* status) {
   int rc = result_ready(ctx); if (rc) return rc;
   const uint64_t n = ctx->last_n;
   std::vector<uint64_t> o, len, ord;
@@ -2345,14 +2311,14 @@ int eh_result_write_files(eh_ctx* ctx, const char* name_template, uint64_t first
   if (!ctx || !name_template) return EH_E_INVALID;
   if (!ctx->have_result) { ctx->err = "no batch has run"; return EH_E_STATE; }
   uint64_t in_b = 0, total = 0, n = 0;
-  int rc = eh_result_totals(ctx, &in_b, &total, &n);
+  int rc = result_totals(ctx, &in_b, &total, &n);
   if (rc) return rc;
   // one case-ordered download (device gather + overlapped copies), then the files are written by a few host threads
   std::vector<uint64_t> off(n + 1); std::vector<int32_t> st(n ? n : 1);
   uint8_t* host = nullptr;
   bool pinned = total > 0 && hipHostMalloc((void**)&host, total, 0) == hipSuccess;
   if (total > 0 && !pinned) { host = (uint8_t*)malloc(total); if (!host) { ctx->err = "eh_result_write_files: out of host memory"; return EH_E_NOMEM; } }
-  rc = eh_result_download(ctx, host, total, off.data(), st.data());
+  rc = result_download(ctx, host, total, off.data(), st.data());
   std::atomic<uint64_t> next{0}, files{0}, bytes{0}, skipped{0}; std::atomic<int> failed{0};
   std::string first_error;
   std::mutex err_lock;
@@ -2604,14 +2570,14 @@ static int uq_result(eh_ctx* ctx, bool dedup) {
 }
 int eh_result_digests(eh_ctx* ctx, uint64_t* digest) {
   if (!ctx) return EH_E_INVALID;
-  CO_GUARD(ctx);
+  std::lock_guard<std::mutex> g(ctx->co_lock); if (int rc = co_idle(ctx)) return rc;
   int rc = uq_result(ctx, false); if (rc) return rc;
   if (digest && ctx->last_n) { HIPCHK(ctx, hipStreamSynchronize(ctx->last_stream)); HIPCHK(ctx, hipMemcpy(digest, ctx->d_uq_digest, ctx->last_n * 8, hipMemcpyDeviceToHost)); }
   return EH_OK;
 }
 int eh_result_unique(eh_ctx* ctx, uint64_t* first_of, uint64_t* n_unique, uint64_t* unique_bytes) {
   if (!ctx) return EH_E_INVALID;
-  CO_GUARD(ctx);
+  std::lock_guard<std::mutex> g(ctx->co_lock); if (int rc = co_idle(ctx)) return rc;
   int rc = uq_result(ctx, true); if (rc) return rc;
   if (first_of && ctx->last_n) HIPCHK(ctx, hipMemcpy(first_of, ctx->d_uq_first, ctx->last_n * 8, hipMemcpyDeviceToHost));
   if (n_unique) *n_unique = ctx->uq_n_unique;
@@ -2620,7 +2586,7 @@ int eh_result_unique(eh_ctx* ctx, uint64_t* first_of, uint64_t* n_unique, uint64
 }
 int eh_result_download_select(eh_ctx* ctx, const uint64_t* idx, uint64_t m, uint8_t* data, uint64_t cap, uint64_t* off) {
   if (!ctx || (!idx && m)) return EH_E_INVALID;
-  CO_GUARD(ctx);
+  std::lock_guard<std::mutex> g(ctx->co_lock); if (int rc = co_idle(ctx)) return rc;
   if (!ctx->have_result) { ctx->err = "no batch has run"; return EH_E_STATE; }
   const uint64_t n = ctx->last_n;
   for (uint64_t k = 0; k < m; k++) if (idx[k] >= n) { ctx->err = "eh_result_download_select: case index outside the last batch"; return EH_E_INVALID; }
@@ -2645,7 +2611,7 @@ int eh_selftest_unique(eh_ctx* ctx, const uint8_t* data, const uint64_t* off, co
   if (!ctx) return EH_E_INVALID;
   if (!off || !status || (!data && off[n])) return EH_E_INVALID;
   for (uint64_t i = 0; i < n; i++) if (off[i] > off[i + 1]) { ctx->err = "eh_selftest_unique: offsets must not decrease"; return EH_E_INVALID; }
-  CO_GUARD(ctx);
+  std::lock_guard<std::mutex> g(ctx->co_lock); if (int rc = co_idle(ctx)) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (ctx->have_result) { int rc = eh_sync(ctx); if (rc) return rc; }
   ctx->uq_digest_seq = ctx->uq_unique_seq = 0;                       // the context's arrays are about to hold this arena's values

@@ -58,8 +58,25 @@ def build_host_oom(force=False):
     return OUT_HOST_OOM
 
 
+OUT_COALESCE_UNIT = os.path.join(ROOT, "build", "coalesce_unit")
+
+
+def build_coalesce_unit(force=False):
+    """coalesce_unit.cpp and the coalescer's bookkeeping header, which needs neither HIP nor the emulator, as a stand-alone
+    program under AddressSanitizer and UndefinedBehaviorSanitizer (see coalesce_unit.cpp)."""
+    main = os.path.join(ROOT, "tests", "hipemu", "coalesce_unit.cpp")
+    deps = [main, os.path.join(ROOT, "erlamsa_amd", "csrc", "eh_coalesce.h"), os.path.join(ROOT, "include", "erlamsa_hip.h")]
+    if not force and os.path.exists(OUT_COALESCE_UNIT) and all(os.path.getmtime(d) <= os.path.getmtime(OUT_COALESCE_UNIT) for d in deps):
+        return OUT_COALESCE_UNIT
+    os.makedirs(os.path.dirname(OUT_COALESCE_UNIT), exist_ok=True)
+    subprocess.check_call(["g++", "-std=c++17", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", main, "-o", OUT_COALESCE_UNIT])
+    return OUT_COALESCE_UNIT
+
+
 if __name__ == "__main__":
-    if "--host-oom" in sys.argv:
+    if "--coalesce-unit" in sys.argv:
+        print(build_coalesce_unit(force="--force" in sys.argv))
+    elif "--host-oom" in sys.argv:
         print(build_host_oom(force="--force" in sys.argv))
     else:
         print(build(force="--force" in sys.argv, race="--race" in sys.argv))
