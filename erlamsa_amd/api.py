@@ -11,6 +11,11 @@ Option keys are the reference's Dict keys (erlamsa_main.erl:127-163):
   skip        cases numbered <= skip are computed but dropped (erlamsa_main.erl:161,191-196)
   unique      (not the reference's: radamsa's --hash) duplicates are found on the device and only one copy of every distinct output
               is downloaded; fuzzer/1 returns the distinct results in first-occurrence order
+  fresh       (not the reference's: radamsa's --checksums N) an int, the capacity of a seen set that the engine of the device keeps
+              across calls (made on first use, kept while the capacity asked for stays the same): outputs that repeat an earlier
+              case of the batch OR an output of an earlier batch are dropped on the device and never downloaded; fuzzer/1 returns
+              only results it has never returned before (cases that `skip` drops count as returned).  Takes precedence over
+              `unique`.  Once more distinct outputs than the capacity have gone by, the surplus is not remembered.
 Only `paths => [direct]`, `output => return` is served by the GPU path.  Keys the reference honours and a batch
 on the GPU cannot - external_mutations (custom mutator funs appended to the table, erlamsa_main.erl:128), external_post (a
 post-processor applied per written block, :159), sequence_muta (:223-235) - raise Unsupported: the caller routes that run to
@@ -20,7 +25,7 @@ import os
 
 import numpy as np
 
-from .engine import CASE_OK, Engine, mutator_table, pattern_table
+from .engine import CASE_OK, SEEN_FRESH, Engine, mutator_table, pattern_table
 
 _engines = {}
 
@@ -91,15 +96,32 @@ def host_only(opts):
 
 
 def fuzz_batch(inputs, opts=None, return_status=False, device=0):
-    """Case I (1-based) of ONE fuzzer/1 run mutates inputs[I-1].  -> list[bytes] (and statuses)."""
+    """Case I (1-based) of ONE fuzzer/1 run mutates inputs[I-1].  -> list[bytes] (and statuses).
+    With opts["unique"] and return_status: (outs, status, first_of).  With opts["fresh"]: the cases that are not fresh come back as b"",
+    and with return_status: (outs, status, cls), cls as eh_result_seen gives it."""
     opts = dict(opts or {})
     if host_only(opts):
         raise Unsupported(host_only(opts))
     eng = _engine(device)
     _configure(eng, opts)
+    if opts.get("fresh"):
+        capacity = int(opts["fresh"])
+        if capacity < 1:
+            raise ValueError("fresh: the capacity of the seen set, a positive int")
+        if eng.seen_count()[1] != capacity:
+            eng.seen_reserve(capacity)
     data, off = pack_corpus(list(inputs))
     eng.upload_corpus(data, off)
     eng.fuzz_batch(seed=_seed_of(opts), first_case=int(opts.get("first_case", 1)), n=len(inputs))
+    if opts.get("fresh"):
+        # only the cases that are neither a repeat inside the batch nor an output of an earlier batch cross PCIe
+        cls, _, _ = eng.result_seen(commit=True)
+        status = eng.status()
+        idx = np.flatnonzero(cls == SEEN_FRESH)
+        outs = [b""] * len(cls)
+        for i, o in zip(idx.tolist(), eng.download_select(idx)):
+            outs[i] = o
+        return (outs, status, cls) if return_status else outs
     if not opts.get("unique"):
         outs, status = eng.download()
         return (outs, status) if return_status else outs
@@ -164,7 +186,8 @@ def fuzzer(opts):
     Like record_result/2 (erlamsa_main.erl:120-122) empty results are dropped (a crashed worker, status 1, gives <<>>).
     A case that stopped at an engine-only limit is never dropped silently: EngineLimit is raised unless
     opts["on_engine_limit"] == "skip" (then the caller reads the statuses through fuzz_batch(return_status=True)).
-    opts["unique"]: the distinct results, each where it first occurs among the cases that are kept."""
+    opts["unique"]: the distinct results, each where it first occurs among the cases that are kept.
+    opts["fresh"]: only the results that no earlier call with the same seen set has returned (and each of them once)."""
     opts = dict(opts)
     if opts.get("paths", ["direct"]) != ["direct"] or opts.get("output", "return") != "return":
         raise ValueError("only paths=[direct], output=return is served by the GPU path")
@@ -174,10 +197,13 @@ def fuzzer(opts):
     skip, first = int(opts.get("skip", 0)), int(opts.get("first_case", 1))
     got = fuzz_batch([bytes(opts.get("input", b""))] * n, opts, return_status=True, device=int(opts.get("device", 0)))
     outs, status = got[0], got[1]
-    first_of = got[2] if opts.get("unique") else range(n)       # without the filter every case is its own first
+    fresh = got[2] == SEEN_FRESH if opts.get("fresh") else None  # with a seen set: the device has said which cases are new
+    first_of = got[2] if opts.get("unique") and fresh is None else range(n)       # without the filter every case is its own first
     res, limited, seen = [], [], set()
     for i, (o, s) in enumerate(zip(outs, status)):
         if first + i <= skip:                                   # `I =< Skip` (erlamsa_main.erl:191): written to the skip port, which keeps nothing
+            continue
+        if s == CASE_OK and fresh is not None and not fresh[i]:
             continue
         if s == CASE_OK and len(o) > 0:
             if int(first_of[i]) not in seen:

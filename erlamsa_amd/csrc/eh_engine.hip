@@ -16,6 +16,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <atomic>
 #include <condition_variable>
 #include <map>
@@ -40,6 +41,7 @@
 #include "eh_zlib.h"
 #include "eh_zip.h"
 #include "eh_unique.h"
+#include "eh_seen.h"
 #include "eh_comm.h"
 #include "eh_coalesce.h"
 
@@ -1272,6 +1274,11 @@ struct eh_ctx {
   DevBuf<unsigned long long> d_uq_tab;                                       // [0] unique cases, [1] their bytes, then owner[slots], rep[slots]
   uint64_t uq_digest_seq = 0, uq_unique_seq = 0, uq_n_unique = 0, uq_bytes = 0;   // batch the device arrays / the two totals belong to (0: none)
   DevBuf<uint64_t> d_sel;                                                    // eh_result_download_select: offsets, lengths, destinations of the listed cases
+  // seen set (eh_seen.h): made by eh_seen_reserve, kept across batches, corpus uploads and eh_configure.  The classification of a batch is
+  // cached like the filter's results (sn_seq), and so is whether its keys have been recorded
+  DevBuf<uint64_t> d_sn_keys, d_sn_pos; DevBuf<unsigned long long> d_sn_tab, d_sn_ctr; DevBuf<uint8_t> d_sn_cls;
+  uint64_t sn_capacity = 0, sn_slots = 0, sn_held = 0, sn_dropped = 0; bool sn_have = false;
+  uint64_t sn_seq = 0, sn_n_fresh = 0, sn_fresh_bytes = 0; bool sn_committed = false;
 };
 
 #define HIPCHK(ctx, call)                                                                             \
@@ -2606,6 +2613,27 @@ int eh_result_download_select(eh_ctx* ctx, const uint64_t* idx, uint64_t m, uint
   HIPCHK(ctx, hipMemcpy(ctx->d_sel, sel.data(), (3 * m + 1) * 8, hipMemcpyHostToDevice));
   return gather_download(ctx, data, m, ctx->d_sel, ctx->d_sel + m, ctx->d_sel + 2 * m, ord, maxlen);
 }
+}  // extern "C"
+
+// A caller-made arena on the device, for the self test hooks: case i = data[off[i] .. off[i + 1]) with status[i]
+struct UqArena { DevBuf<uint8_t> data; DevBuf<uint64_t> off, len; DevBuf<int32_t> status; uint64_t pieces = 0; };
+static int uq_upload_arena(eh_ctx* ctx, UqArena& a, const uint8_t* data, const uint64_t* off, const int32_t* status, uint64_t n) {
+  const uint64_t nbytes = off[n] - off[0];
+  std::vector<uint64_t> len(n), rel(n);
+  for (uint64_t i = 0; i < n; i++) { len[i] = off[i + 1] - off[i]; rel[i] = off[i] - off[0]; a.pieces += (len[i] + UQ_PIECE - 1) / UQ_PIECE; }
+  HIPCHK(ctx, a.data.grow(nbytes ? nbytes : 1));
+  HIPCHK(ctx, a.off.grow(n));
+  HIPCHK(ctx, a.len.grow(n));
+  HIPCHK(ctx, a.status.grow(n));
+  if (nbytes) HIPCHK(ctx, hipMemcpy(a.data, data + off[0], nbytes, hipMemcpyHostToDevice));
+  HIPCHK(ctx, hipMemcpy(a.off, rel.data(), n * 8, hipMemcpyHostToDevice));
+  HIPCHK(ctx, hipMemcpy(a.len, len.data(), n * 8, hipMemcpyHostToDevice));
+  HIPCHK(ctx, hipMemcpy(a.status, status, n * 4, hipMemcpyHostToDevice));
+  return EH_OK;
+}
+
+extern "C" {
+
 // Self test hook: the same kernels over a caller-made arena (case i = data[off[i] .. off[i + 1]), status[i]); digest / first_of may be NULL.
 int eh_selftest_unique(eh_ctx* ctx, const uint8_t* data, const uint64_t* off, const int32_t* status, uint64_t n, uint64_t* digest, uint64_t* first_of) {
   if (!ctx) return EH_E_INVALID;
@@ -2616,20 +2644,9 @@ int eh_selftest_unique(eh_ctx* ctx, const uint8_t* data, const uint64_t* off, co
   if (ctx->have_result) { int rc = eh_sync(ctx); if (rc) return rc; }
   ctx->uq_digest_seq = ctx->uq_unique_seq = 0;                       // the context's arrays are about to hold this arena's values
   if (!n) return EH_OK;
-  const uint64_t nbytes = off[n] - off[0];
-  std::vector<uint64_t> len(n); uint64_t pieces = 0;
-  for (uint64_t i = 0; i < n; i++) { len[i] = off[i + 1] - off[i]; pieces += (len[i] + UQ_PIECE - 1) / UQ_PIECE; }
-  DevBuf<uint8_t> dd; DevBuf<uint64_t> dof, dl; DevBuf<int32_t> ds;
-  HIPCHK(ctx, dd.grow(nbytes ? nbytes : 1));
-  HIPCHK(ctx, dof.grow(n));
-  HIPCHK(ctx, dl.grow(n));
-  HIPCHK(ctx, ds.grow(n));
-  if (nbytes) HIPCHK(ctx, hipMemcpy(dd, data + off[0], nbytes, hipMemcpyHostToDevice));
-  std::vector<uint64_t> rel(n); for (uint64_t i = 0; i < n; i++) rel[i] = off[i] - off[0];
-  HIPCHK(ctx, hipMemcpy(dof, rel.data(), n * 8, hipMemcpyHostToDevice));
-  HIPCHK(ctx, hipMemcpy(dl, len.data(), n * 8, hipMemcpyHostToDevice));
-  HIPCHK(ctx, hipMemcpy(ds, status, n * 4, hipMemcpyHostToDevice));
-  int rc = uq_launch(ctx, dd, dof, dl, ds, n, pieces, true, first_of != nullptr, nullptr);
+  UqArena a;
+  int rc = uq_upload_arena(ctx, a, data, off, status, n); if (rc) return rc;
+  rc = uq_launch(ctx, a.data, a.off, a.len, a.status, n, a.pieces, true, first_of != nullptr, nullptr);
   if (rc) return rc;
   HIPCHK(ctx, hipStreamSynchronize(nullptr));
   if (digest) HIPCHK(ctx, hipMemcpy(digest, ctx->d_uq_digest, n * 8, hipMemcpyDeviceToHost));
@@ -2637,4 +2654,174 @@ int eh_selftest_unique(eh_ctx* ctx, const uint8_t* data, const uint64_t* off, co
   return EH_OK;
 }
 
+// ---- seen set (csrc/eh_seen.h) ----------------------------------------------------------------------------------------------------
+static void sn_drop(eh_ctx* ctx) {
+  ctx->d_sn_keys.release(); ctx->d_sn_tab.release(); ctx->d_sn_ctr.release(); ctx->d_sn_pos.release(); ctx->d_sn_cls.release();
+  ctx->sn_capacity = ctx->sn_slots = ctx->sn_held = ctx->sn_dropped = ctx->sn_seq = 0; ctx->sn_have = false; ctx->sn_committed = false;
+}
+static int sn_need(eh_ctx* ctx) {
+  if (ctx->sn_have) return EH_OK;
+  ctx->err = "no seen set: eh_seen_reserve makes one"; return EH_E_STATE;
+}
+// Classifies n cases given by their lengths, digests and the filter's results (`lookup`) and / or records the keys of the fresh ones
+// (`commit`), then reads the counters back: *fresh / *fresh_bytes = the cases of class 0.  d_status, d_first and d_flag may be null
+// (eh_seen.h).  Returns with `st` idle.
+static int sn_run(eh_ctx* ctx, const uint64_t* d_len, const int32_t* d_status, const uint64_t* d_digest, const uint64_t* d_first, const uint32_t* d_flag, uint64_t n,
+                  bool lookup, bool commit, hipStream_t st, uint64_t* fresh, uint64_t* fresh_bytes) {
+  *fresh = *fresh_bytes = 0;
+  if (!n) return EH_OK;
+  HIPCHK(ctx, ctx->d_sn_cls.grow(n));
+  HIPCHK(ctx, ctx->d_sn_pos.grow(n));
+  const uint32_t gc = uq_grid(ctx, (n + 63) / 64);
+  if (lookup)
+    hipLaunchKernelGGL(eh_sn_lookup_kernel, dim3(gc), dim3(64), 0, st, d_len, d_status, d_digest, d_first, n, (const uint64_t*)ctx->d_sn_keys, (const unsigned long long*)ctx->d_sn_tab, ctx->sn_slots,
+                       ctx->d_sn_cls);
+  hipLaunchKernelGGL(eh_sn_rank_kernel, dim3(1), dim3(64), 0, st, d_len, (const uint8_t*)ctx->d_sn_cls, d_flag, n, ctx->sn_capacity, commit ? 1u : 0u, ctx->d_sn_ctr, ctx->d_sn_pos);
+  if (commit) {
+    hipLaunchKernelGGL(eh_sn_append_kernel, dim3(gc), dim3(64), 0, st, d_len, d_digest, (const uint64_t*)ctx->d_sn_pos, n, ctx->d_sn_keys);
+    hipLaunchKernelGGL(eh_sn_insert_kernel, dim3(gc), dim3(64), 0, st, (const uint64_t*)ctx->d_sn_pos, n, (const uint64_t*)ctx->d_sn_keys, ctx->d_sn_tab, ctx->sn_slots);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  unsigned long long c[4] = {0, 0, 0, 0};
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  HIPCHK(ctx, hipMemcpy(c, ctx->d_sn_ctr, sizeof(c), hipMemcpyDeviceToHost));
+  ctx->sn_held = c[0]; ctx->sn_dropped = c[1]; *fresh = c[2]; *fresh_bytes = c[3];
+  return EH_OK;
+}
+int eh_seen_reserve(eh_ctx* ctx, uint64_t capacity) {
+  if (!ctx) return EH_E_INVALID;
+  std::lock_guard<std::mutex> g(ctx->co_lock); if (int rc = co_idle(ctx)) return rc;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (ctx->have_result) { int rc = eh_sync(ctx); if (rc) return rc; }
+  sn_drop(ctx);
+  if (!capacity) return EH_OK;
+  if (capacity > (1ull << 40)) { ctx->err = "eh_seen_reserve: no memory for a set of that capacity"; return EH_E_NOMEM; }
+  uint64_t slots = 2; while (slots < 2 * capacity) slots <<= 1;
+  if (ctx->d_sn_keys.reset(2 * capacity) != hipSuccess || ctx->d_sn_tab.reset(slots) != hipSuccess || ctx->d_sn_ctr.reset(4) != hipSuccess) {
+    (void)hipGetLastError(); sn_drop(ctx); ctx->err = "eh_seen_reserve: out of device memory"; return EH_E_NOMEM;
+  }
+  HIPCHK(ctx, hipMemset(ctx->d_sn_tab, 0xFF, slots * 8));             // every word SN_EMPTY
+  HIPCHK(ctx, hipMemset(ctx->d_sn_ctr, 0, 4 * 8));
+  HIPCHK(ctx, hipDeviceSynchronize());
+  ctx->sn_capacity = capacity; ctx->sn_slots = slots; ctx->sn_have = true;
+  return EH_OK;
+}
+int eh_seen_count(eh_ctx* ctx, uint64_t out[4]) {
+  if (!ctx || !out) return EH_E_INVALID;
+  std::lock_guard<std::mutex> g(ctx->co_lock);
+  out[0] = ctx->sn_held; out[1] = ctx->sn_capacity; out[2] = ctx->sn_dropped; out[3] = ctx->sn_slots;      // (all 0 without a set)
+  return EH_OK;
+}
+int eh_seen_add_keys(eh_ctx* ctx, const uint64_t* keys, uint64_t m, uint64_t* added) {
+  if (!ctx || (!keys && m)) return EH_E_INVALID;
+  std::lock_guard<std::mutex> g(ctx->co_lock); if (int rc = co_idle(ctx)) return rc;
+  if (int rc = sn_need(ctx)) return rc;
+  for (uint64_t k = 0; k < m; k++) if (keys[2 * k] >> 63) { ctx->err = "eh_seen_add_keys: a length of 2^63 or more"; return EH_E_INVALID; }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (ctx->have_result) { int rc = eh_sync(ctx); if (rc) return rc; }
+  if (added) *added = 0;
+  // the first occurrence of every key of the list, in list order: what is left is distinct, as the ranked cases of a batch are
+  std::vector<uint64_t> len, dig;
+  try {
+    std::vector<uint64_t> ix(m);
+    for (uint64_t k = 0; k < m; k++) ix[k] = k;
+    std::sort(ix.begin(), ix.end(), [&](uint64_t a, uint64_t b) {
+      if (keys[2 * a] != keys[2 * b]) return keys[2 * a] < keys[2 * b];
+      if (keys[2 * a + 1] != keys[2 * b + 1]) return keys[2 * a + 1] < keys[2 * b + 1];
+      return a < b;
+    });
+    std::vector<uint8_t> firstk(m, 0);
+    for (uint64_t k = 0; k < m; k++) firstk[ix[k]] = !k || keys[2 * ix[k]] != keys[2 * ix[k - 1]] || keys[2 * ix[k] + 1] != keys[2 * ix[k - 1] + 1];
+    for (uint64_t k = 0; k < m; k++) if (firstk[k]) { len.push_back(keys[2 * k]); dig.push_back(keys[2 * k + 1]); }
+  } catch (const std::bad_alloc&) { ctx->err = "out of host memory"; return EH_E_NOMEM; }
+  const uint64_t n = len.size();
+  if (!n) return EH_OK;
+  ctx->sn_seq = 0;                                                   // the set changes, and cls / pos are about to hold the list's values
+  DevBuf<uint64_t> dl, dd;
+  HIPCHK(ctx, dl.grow(n));
+  HIPCHK(ctx, dd.grow(n));
+  HIPCHK(ctx, hipMemcpy(dl, len.data(), n * 8, hipMemcpyHostToDevice));
+  HIPCHK(ctx, hipMemcpy(dd, dig.data(), n * 8, hipMemcpyHostToDevice));
+  const uint64_t before = ctx->sn_held;
+  uint64_t f, fb;
+  int rc = sn_run(ctx, dl, nullptr, dd, nullptr, nullptr, n, true, true, ctx->last_stream, &f, &fb); if (rc) return rc;
+  if (added) *added = ctx->sn_held - before;
+  return EH_OK;
+}
+int eh_seen_add_corpus(eh_ctx* ctx, uint64_t* added) {
+  if (!ctx) return EH_E_INVALID;
+  std::lock_guard<std::mutex> g(ctx->co_lock); if (int rc = co_idle(ctx)) return rc;
+  if (int rc = sn_need(ctx)) return rc;
+  if (!ctx->d_corpus) { ctx->err = "no corpus loaded"; return EH_E_STATE; }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (ctx->have_result) { int rc = eh_sync(ctx); if (rc) return rc; }
+  if (added) *added = 0;
+  const uint64_t n = ctx->n_corpus;
+  if (!n) return EH_OK;
+  ctx->uq_digest_seq = ctx->uq_unique_seq = ctx->sn_seq = 0;         // the filter's arrays and cls / pos are about to hold the corpus's values
+  DevBuf<uint64_t> dl; DevBuf<int32_t> ds;
+  HIPCHK(ctx, dl.grow(n));
+  HIPCHK(ctx, ds.grow(n));
+  hipStream_t st = ctx->last_stream;
+  HIPCHK(ctx, hipMemsetAsync(ds, 0, n * 4, st));                      // every entry a candidate (EH_CASE_OK)
+  uint64_t* d_len = dl;
+  hipLaunchKernelGGL(eh_sn_lens_kernel, dim3(uq_grid(ctx, (n + 63) / 64)), dim3(64), 0, st, (const uint64_t*)ctx->d_coff, d_len, n);
+  // the filter first: equal entries add one key, their first's
+  int rc = uq_launch(ctx, ctx->d_corpus, ctx->d_coff, dl, ds, n, n + ctx->corpus_bytes / UQ_PIECE + 1, true, true, st); if (rc) return rc;
+  const uint64_t before = ctx->sn_held;
+  uint64_t f, fb;
+  rc = sn_run(ctx, dl, ds, ctx->d_uq_digest, ctx->d_uq_first, ctx->d_uq_flag, n, true, true, st, &f, &fb); if (rc) return rc;
+  if (added) *added = ctx->sn_held - before;
+  return EH_OK;
+}
+int eh_seen_export(eh_ctx* ctx, uint64_t* keys, uint64_t cap_keys, uint64_t* n) {
+  if (!ctx || (!keys && cap_keys)) return EH_E_INVALID;
+  std::lock_guard<std::mutex> g(ctx->co_lock); if (int rc = co_idle(ctx)) return rc;
+  if (int rc = sn_need(ctx)) return rc;
+  if (n) *n = ctx->sn_held;
+  const uint64_t m = ctx->sn_held < cap_keys ? ctx->sn_held : cap_keys;
+  if (!m) return EH_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  HIPCHK(ctx, hipMemcpy(keys, ctx->d_sn_keys, m * 16, hipMemcpyDeviceToHost));
+  return EH_OK;
+}
+int eh_result_seen(eh_ctx* ctx, uint32_t commit, uint8_t* cls, uint64_t* n_fresh, uint64_t* fresh_bytes) {
+  if (!ctx) return EH_E_INVALID;
+  std::lock_guard<std::mutex> g(ctx->co_lock); if (int rc = co_idle(ctx)) return rc;
+  if (int rc = sn_need(ctx)) return rc;
+  int rc = uq_result(ctx, true); if (rc) return rc;                   // digests, first_of and the flags of the last batch (EH_E_STATE before one)
+  const uint64_t n = ctx->last_n;
+  const bool lookup = ctx->sn_seq != ctx->batch_seq;
+  const bool record = commit && (lookup || !ctx->sn_committed);
+  if (lookup || record) {
+    uint64_t f, fb;
+    rc = sn_run(ctx, ctx->d_len, ctx->d_status, ctx->d_uq_digest, ctx->d_uq_first, ctx->d_uq_flag, n, lookup, record, ctx->last_stream, &f, &fb); if (rc) return rc;
+    if (lookup) { ctx->sn_n_fresh = f; ctx->sn_fresh_bytes = fb; ctx->sn_committed = false; }
+    if (record) ctx->sn_committed = true;
+    ctx->sn_seq = ctx->batch_seq;
+  }
+  if (cls && n) HIPCHK(ctx, hipMemcpy(cls, ctx->d_sn_cls, n, hipMemcpyDeviceToHost));
+  if (n_fresh) *n_fresh = ctx->sn_n_fresh;
+  if (fresh_bytes) *fresh_bytes = ctx->sn_fresh_bytes;
+  return EH_OK;
+}
+// Self test hook: the filter's and the set's kernels over a caller-made arena, as eh_selftest_unique; cls (n entries) may be NULL.
+int eh_selftest_seen(eh_ctx* ctx, const uint8_t* data, const uint64_t* off, const int32_t* status, uint64_t n, uint32_t commit, uint8_t* cls) {
+  if (!ctx) return EH_E_INVALID;
+  if (!off || !status || (!data && off[n])) return EH_E_INVALID;
+  for (uint64_t i = 0; i < n; i++) if (off[i] > off[i + 1]) { ctx->err = "eh_selftest_seen: offsets must not decrease"; return EH_E_INVALID; }
+  std::lock_guard<std::mutex> g(ctx->co_lock); if (int rc = co_idle(ctx)) return rc;
+  if (int rc = sn_need(ctx)) return rc;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (ctx->have_result) { int rc = eh_sync(ctx); if (rc) return rc; }
+  ctx->uq_digest_seq = ctx->uq_unique_seq = ctx->sn_seq = 0;         // the context's arrays are about to hold this arena's values
+  if (!n) return EH_OK;
+  UqArena a;
+  int rc = uq_upload_arena(ctx, a, data, off, status, n); if (rc) return rc;
+  rc = uq_launch(ctx, a.data, a.off, a.len, a.status, n, a.pieces, true, true, nullptr); if (rc) return rc;
+  uint64_t f, fb;
+  rc = sn_run(ctx, a.len, a.status, ctx->d_uq_digest, ctx->d_uq_first, ctx->d_uq_flag, n, true, commit != 0, nullptr, &f, &fb); if (rc) return rc;
+  if (cls) HIPCHK(ctx, hipMemcpy(cls, ctx->d_sn_cls, n, hipMemcpyDeviceToHost));
+  return EH_OK;
+}
 }  // extern "C"

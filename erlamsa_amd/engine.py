@@ -38,7 +38,10 @@ ABI_SYMBOLS = [
     "eh_corpus_broadcast_local", "eh_device_count", "eh_meta_atom_count", "eh_meta_atom_name", "eh_batch_done",
     "eh_result_digests", "eh_result_unique", "eh_result_download_select", "eh_selftest_unique",
     "eh_profile_add", "eh_profile_count", "eh_fuzz_calls_profiled", "eh_submit_profiled",
+    "eh_seen_reserve", "eh_seen_count", "eh_seen_add_keys", "eh_seen_add_corpus", "eh_seen_export", "eh_result_seen", "eh_selftest_seen",
 ]
+
+SEEN_FRESH, SEEN_IN_BATCH, SEEN_BEFORE, SEEN_NOT_OK = 0, 1, 2, 3   # cls[i] of eh_result_seen
 
 MAX_PROFILES = 1024   # EH_MAX_PROFILES
 
@@ -104,6 +107,13 @@ def load_library():
     lib.eh_result_unique.argtypes = [vp, vp, u64p, u64p]
     lib.eh_result_download_select.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp]
     lib.eh_selftest_unique.argtypes = [vp, vp, vp, vp, C.c_uint64, vp, vp]
+    lib.eh_seen_reserve.argtypes = [vp, C.c_uint64]
+    lib.eh_seen_count.argtypes = [vp, vp]
+    lib.eh_seen_add_keys.argtypes = [vp, vp, C.c_uint64, u64p]
+    lib.eh_seen_add_corpus.argtypes = [vp, u64p]
+    lib.eh_seen_export.argtypes = [vp, vp, C.c_uint64, u64p]
+    lib.eh_result_seen.argtypes = [vp, C.c_uint32, vp, u64p, u64p]
+    lib.eh_selftest_seen.argtypes = [vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp]
     lib.eh_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
     lib.eh_pool_stats.argtypes = [vp, vp]
     lib.eh_result_summary.argtypes = [vp, vp]
@@ -467,6 +477,57 @@ class Engine:
         self._chk(self.lib.eh_selftest_unique(self.h, data.ctypes.data, off.ctypes.data, status.ctypes.data, n, dig.ctypes.data,
                                               first.ctypes.data if dedup else None))
         return dig[:n], (first[:n] if dedup else None)
+
+    # ---- seen set: outputs of earlier batches, dropped on the device (eh_seen_reserve .. eh_result_seen)
+    def seen_reserve(self, capacity):
+        """an empty seen set of `capacity` keys (length, digest) on this context; 0 drops the set"""
+        self._chk(self.lib.eh_seen_reserve(self.h, int(capacity)))
+
+    def seen_count(self):
+        """-> (keys held, capacity, keys dropped because the set was full, table slots); zeros without a set"""
+        v = np.zeros(4, dtype=np.uint64)
+        self._chk(self.lib.eh_seen_count(self.h, v.ctypes.data))
+        return tuple(int(x) for x in v)
+
+    def seen_add_keys(self, keys):
+        """keys: m pairs (length, digest), e.g. what seen_export gave -> how many were added (repeats and known keys are not)"""
+        k = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1, 2)
+        added = C.c_uint64()
+        self._chk(self.lib.eh_seen_add_keys(self.h, k.ctypes.data, len(k), C.byref(added)))
+        return added.value
+
+    def seen_add_corpus(self):
+        """the key of every entry of the loaded corpus: an output that equals any seed is then seen -> keys added"""
+        added = C.c_uint64()
+        self._chk(self.lib.eh_seen_add_corpus(self.h, C.byref(added)))
+        return added.value
+
+    def seen_export(self):
+        """-> uint64[held, 2]: the keys (length, digest) in the order they were first seen"""
+        n = C.c_uint64()
+        self._chk(self.lib.eh_seen_export(self.h, None, 0, C.byref(n)))
+        k = np.zeros((max(n.value, 1), 2), dtype=np.uint64)
+        self._chk(self.lib.eh_seen_export(self.h, k.ctypes.data, n.value, C.byref(n)))
+        return k[:n.value]
+
+    def result_seen(self, commit=True):
+        """-> (cls uint8[n], n_fresh, fresh_bytes) of the last batch: 0 fresh, 1 a repeat inside the batch, 2 seen in an earlier
+        batch, 3 not EH_CASE_OK; commit records the fresh cases' keys (once per batch) - eh_result_seen"""
+        n = self.last_n
+        cls = np.zeros(max(n, 1), dtype=np.uint8)
+        nf, nb = C.c_uint64(), C.c_uint64()
+        self._chk(self.lib.eh_result_seen(self.h, 1 if commit else 0, cls.ctypes.data, C.byref(nf), C.byref(nb)))
+        return cls[:n], nf.value, nb.value
+
+    def selftest_seen(self, data, off, status, commit=True):
+        """the filter's and the set's kernels over a caller-made arena (case i = data[off[i]:off[i+1]]) -> cls uint8[n]"""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        status = np.ascontiguousarray(status, dtype=np.int32)
+        n = len(off) - 1
+        cls = np.zeros(max(n, 1), dtype=np.uint8)
+        self._chk(self.lib.eh_selftest_seen(self.h, data.ctypes.data, off.ctypes.data, status.ctypes.data, n, 1 if commit else 0, cls.ctypes.data))
+        return cls[:n]
 
     def download_into(self, host_ptr, cap):
         """Case-ordered outputs of the last batch into caller memory at `host_ptr` (`cap` bytes; pinned or registered

@@ -342,7 +342,7 @@ int eh_result_meta(eh_ctx* ctx, uint64_t i, uint8_t* buf, uint64_t cap, uint64_t
  *                    says what is needed (data = NULL asks for the sizes only).
  * All three: EH_E_STATE before a batch has run and on a context that has coalesced requests pending or in flight.  The results are
  * kept per batch (a second call copies, it does not compute) and dropped by the next eh_fuzz_batch / eh_fuzz_calls.  A filter that
- * persists across batches (radamsa's --checksums N) is the host's: the digests are what it would keep.
+ * persists across batches (radamsa's --checksums N) is the seen set below.
  * EH_UNIQUE_PIECE_BYTES: both passes cut every case into pieces of this many bytes and hand the pieces, not the cases, to the
  * wavefronts (a diagnostic constant: tests place cases around its multiples). */
 #define EH_UNIQUE_PIECE_BYTES 65536
@@ -353,6 +353,65 @@ int eh_result_download_select(eh_ctx* ctx, const uint64_t* idx, uint64_t m, uint
  * data[off[i] .. off[i+1]) with status[i]; digest and first_of (n entries each) may be NULL. */
 int eh_selftest_unique(eh_ctx* ctx, const uint8_t* data, const uint64_t* off, const int32_t* status, uint64_t n,
                        uint64_t* digest, uint64_t* first_of);
+
+/* ---- seen set: the outputs of EARLIER batches, dropped on the device (added within ABI 8; kernels in csrc/eh_seen.h).  Reference
+ * counterpart: radamsa's --checksums N, the checksum set it keeps over its whole run.  The uniqueness filter above finds the repeats
+ * inside one batch and forgets; a run is many batches, and the commonest useless output of all - one that equals its own seed - is in
+ * no batch.  A seen set belongs to a context and holds up to `capacity` keys, a key being (length, digest) of an output.  It
+ * survives batches, corpus uploads and eh_configure (a digest is a function of the output bytes alone); eh_seen_reserve and
+ * eh_destroy drop it.
+ *
+ * eh_seen_reserve     makes an empty set of `capacity` keys (whatever set there was is dropped); capacity 0 drops the set and frees
+ *                     its memory.  EH_E_NOMEM when the memory cannot be had (there is no set then).
+ * eh_seen_count       out[0] keys held, out[1] capacity, out[2] keys dropped because the set was full since the last
+ *                     eh_seen_reserve, out[3] slots of the hash table (the power of two >= 2 capacity).  All 0 without a set.
+ * eh_seen_add_keys    m pairs {length, digest} from outside (another context's or an earlier set's export).  Repeats inside the list
+ *                     and keys already present are ignored, the others are added in list order; *added = how many were.
+ *                     EH_E_INVALID for a length of 2^63 or more.
+ * eh_seen_add_corpus  digests every entry of the loaded corpus on the device and adds the keys in entry order (equal entries add one
+ *                     key): an output that equals ANY seed is then seen.  EH_E_STATE without a corpus.
+ * eh_seen_export      the keys in the order they were first seen, as {length, digest} pairs: min(*n, cap_keys) pairs are copied and
+ *                     *n = keys held either way, so (keys = NULL, cap_keys = 0) asks for the count.
+ * eh_result_seen      classifies the last batch and, with commit != 0, records the keys of its fresh cases.  cls[i] is, the first row
+ *                     that holds deciding:
+ *                       3  case i did not end EH_CASE_OK (it is not looked at)
+ *                       1  first_of[i] != i: the same bytes as an earlier case of this batch, by eh_result_unique's rule
+ *                       2  the case's key was in the set before this batch
+ *                       0  otherwise: fresh
+ *                     *n_fresh / *fresh_bytes = the cases of class 0 and the sum of their lengths.  cls (n entries), n_fresh and
+ *                     fresh_bytes may each be NULL.
+ * eh_selftest_seen    self test hook (tests only): the same kernels over a caller-made arena, as eh_selftest_unique; a "batch" of a few
+ *                     planted cases.  cls may be NULL.
+ * EH_E_STATE: all but eh_seen_reserve and eh_seen_count without a set; eh_result_seen before a batch has run; all but
+ * eh_seen_count on a context that has coalesced requests pending or in flight.
+ *
+ * Deterministic.  The classes and the set's contents IN EXPORT ORDER depend only on the sequence of calls and their bytes, never on
+ *   scheduling: within a batch (a key list, a corpus) keys are recorded in case-index order.
+ * Flagged cases.  eh_result_unique's collision rule can leave a case reported unique although it shares length and digest with an
+ *   earlier case of the batch whose bytes differ.  Such a case shares that first case's key: it is class 0 unless the key was in the
+ *   set before the batch (then 2), and it records no key of its own.  No two cases of one batch ever lose distinct bytes to each other.
+ * Idempotent per batch.  The classification is kept per batch like the filter's results: a second eh_result_seen for the same batch
+ *   returns the same classes and does not classify again (every fresh case would read as 2 otherwise).  commit = 0 and later
+ *   commit != 0 for the same batch records the keys of the kept classification, exactly once.  The next launch drops it, and so does
+ *   a call that changes the set from outside or borrows the arrays (eh_seen_reserve, eh_seen_add_keys, eh_seen_add_corpus,
+ *   eh_selftest_seen): eh_result_seen after one of those classifies the batch against the set as it is then.
+ * Full set.  Fresh keys beyond the capacity are not recorded: those that fit are taken in case-index order, the rest are counted in
+ *   out[2], and their cases are class 0 all the same.  A full set never calls anything seen that is not in it.  The caller exports,
+ *   reserves a larger set and adds the keys back.
+ * What "seen" means across batches.  The earlier outputs no longer exist, so class 2 rests on the length and both CRCs and NOT on a
+ *   byte compare: two different outputs of equal length and digest in different batches make the later one class 2.  Such a pair
+ *   can be constructed (see eh_result_unique); by chance it is of the order of n m / 2^64 for n cases against m keys.  Class 1 keeps
+ *   the byte-exact rule it has.
+ * Value range.  Every 64-bit digest value is a legal key, 0 (the empty output: key (0, 0)) and ~0 included; lengths are below 2^63.
+ *   The table's empty marker lives in a word that holds an index into the key log, never in a key. */
+int eh_seen_reserve(eh_ctx* ctx, uint64_t capacity);
+int eh_seen_count(eh_ctx* ctx, uint64_t out[4]);
+int eh_seen_add_keys(eh_ctx* ctx, const uint64_t* keys, uint64_t m, uint64_t* added);
+int eh_seen_add_corpus(eh_ctx* ctx, uint64_t* added);
+int eh_seen_export(eh_ctx* ctx, uint64_t* keys, uint64_t cap_keys, uint64_t* n);
+int eh_result_seen(eh_ctx* ctx, uint32_t commit, uint8_t* cls, uint64_t* n_fresh, uint64_t* fresh_bytes);
+int eh_selftest_seen(eh_ctx* ctx, const uint8_t* data, const uint64_t* off, const int32_t* status, uint64_t n, uint32_t commit,
+                     uint8_t* cls);
 
 /* Per-case high-water mark of work memory in bytes (diagnostic; what sizes max_case_bytes and the pool's tiers). */
 int eh_result_peak(eh_ctx* ctx, uint64_t* peak);
