@@ -1,6 +1,6 @@
 // eh_coalesce.h — the bookkeeping of the request coalescer (eh_submit / eh_flush / eh_poll / eh_cancel), host side, no HIP, no eh_ctx:
-// which requests wait for a launch, which tickets are on the device, which results wait to be polled.  eh_engine.hip keeps one
-// Coalescer per context behind a std::mutex and does the launches and downloads; tests/hipemu/coalesce_unit.cpp checks this file alone.
+// which requests wait for a launch, which tickets are on the device, which results wait to be polled.  The context (eh_host.h) keeps
+// one Coalescer behind a std::mutex, and eh_host_coalesce.h does the launches and downloads; tests/hipemu/coalesce_unit.cpp checks this file alone.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

@@ -199,7 +199,7 @@ struct KParams {
   EH_G unsigned long long* in_bytes;
   // Work areas.  Workgroup w of a batch owns slot w of the context (block tables + work_cap bytes of work area): a slot per
   // launched workgroup, so no wavefront ever waits for one.  A case that outgrows what it holds borrows a larger area from
-  // a POOL all contexts of the device share (eh_engine.hip, DevPool; tiers 1..ntiers, twice the area per tier up to
+  // a POOL all contexts of the device share (eh_host.h DevPool, eh_host_pool.h; tiers 1..ntiers, twice the area per tier up to
   // big_case_bytes) and goes on there; only the mutator attempt that ran out of memory is repeated (eh_device.h, ws_regrow).
   // Every tier is a ring of free area indices: pool_ctr[2t] = pop tickets, pool_ctr[2t+1] = push tickets,
   // pool_ctr[20+t] = ticks wavefronts waited for an area of tier t, pool_ctr[30+t] = how many had to wait.

@@ -195,7 +195,7 @@ EH_DEV uint32_t ldg4(const EH_G void* p) { return *reinterpret_cast<const EH_G e
 // Copies of CO_COPY_MIN bytes and more inside a case are posted for several wavefronts (co_copy below); the _raw forms are the
 // loops themselves (one wavefront), for the kernels that are not cases and for the chunks of a posted copy.
 // CO_COPY_MIN: what the inlined test at every call site compares with; the size from which a copy IS posted and its chunks are run-time
-// parameters (KParams co_copy_min >= CO_COPY_MIN, co_copy_chunk; eh_engine.hip co_defaults).
+// parameters (KParams co_copy_min >= CO_COPY_MIN, co_copy_chunk; eh_host_pool.h co_defaults).
 #ifdef HIPEMU
 constexpr uint32_t CO_COPY_MIN = 8u << 10;         // (the emulator's tests are small: they take the posted path too, one wavefront running every chunk)
 #else
@@ -296,7 +296,7 @@ EH_DEV bool wave_equal(cbptr a, cbptr b, uint32_t n) {
 // ---------------------------------------------------------------------------------------------
 // Per-case context (all wave-uniform)
 // ---------------------------------------------------------------------------------------------
-// site: 1xx eh_device.h, 2xx eh_doc.h, 3xx eh_engine.hip, 4xx eh_json.h, 5xx eh_lex.h, 6xx eh_sgml.h, 7xx eh_text.h, 8xx eh_tree.h
+// site: 1xx eh_device.h, 2xx eh_doc.h, 3xx eh_patterns.h and eh_gen.h, 4xx eh_json.h, 5xx eh_lex.h, 6xx eh_sgml.h, 7xx eh_text.h, 8xx eh_tree.h
 constexpr int MAX_CHUNKS = POOL_TIERS + 1;
 constexpr int MAX_NEST = 6;         // nested scheduler calls (b64 / sgm / js inner mutations)
 constexpr int LEX_LEVELS = MAX_NEST + 1;
@@ -353,9 +353,9 @@ struct Ctx {
   uint64_t ovf_need, ovf_req;   // work area the case had asked for in total / in the request that failed (0: unknown): picks the tier that runs it again
   int ovf_line;        // site id that set CASE_OVERFLOW (diagnostic: reported as -line in the last-mutator array)
   int depth;           // nesting depth of mux_fuzzers (b64 / sgm / js inner mutations re-enter the scheduler)
-  int gen_pending;     // G_FILE / G_JUMP: the generator's fun has not been called yet (gen_force, eh_engine.hip); 0 = Ll is a list
+  int gen_pending;     // G_FILE / G_JUMP: the generator's fun has not been called yet (gen_force, eh_gen.h); 0 = Ll is a list
   uint32_t gen_e1, gen_e2;   // the corpus entries (paths) it was made for
-  int pat_ret; uint32_t pat_ip; int pat_cont;   // results of the container patterns' helpers (cp_end / ar_step, eh_engine.hip)  // eh_fuse_red.h: the search runs on shortened lists and only names its node (fp_on); the members are found in the originals
+  int pat_ret; uint32_t pat_ip; int pat_cont;   // results of the container patterns' helpers (cp_end / ar_step, eh_patterns.h)  // eh_fuse_red.h: the search runs on shortened lists and only names its node (fp_on); the members are found in the originals
   uint32_t fp_on, fp_g, fp_special, fp_keypos, fp_bA, fp_bB;
 };
 // The per-case context lives in LDS.  One workgroup is one wavefront, so there is exactly one Ctx per
@@ -383,7 +383,7 @@ EH_DEV void lanes_sync() { (void)__ballot(1); }
 #define EH_CTX Ctx& c = g_ctx
 // The LDS band of the fuse mutators (eh_fuse.h, eh_fuse2.h, eh_fuse_lds.h) and the sgm tokenizer.  Outside of them it is free, and
 // the pattern-level finders stage their tables there: the CRC tables of wave_crc32 (eh_zlib.h), the right ends and counts of
-// pick_simple_len (eh_field.h), the prefix CRCs and hit masks of pick_csum (eh_engine.hip).  Nobody keeps anything in it across calls.
+// pick_simple_len (eh_field.h), the prefix CRCs and hit masks of pick_csum (eh_patterns.h).  Nobody keeps anything in it across calls.
 #ifndef EH_FUSE_LDS_WORDS
 #define EH_FUSE_LDS_WORDS 4800
 #endif

@@ -3,7 +3,7 @@
 // erlamsa_utils:sort_by_priority/1 (reference src/erlamsa_utils.erl:113-117) hands lists:sort/2 a strict '>' as the
 // ordering fun, so the order among equal priorities — which decides every weighted choice of mutator, pattern and
 // generator — is whatever stdlib's merge sort does with a fun that is not a total "=<".  The engine's host set-up
-// (eh_engine.hip) uses this header and nothing else does: oracle/otp_compat.h has a restatement of its own (cons lists, clause
+// (eh_host_options.h) uses this header and nothing else does: oracle/otp_compat.h has a restatement of its own (cons lists, clause
 // for clause from stdlib's lists.erl) and tests/pymodel.py a third one in Python; tests/test_pymodel.py
 // (test_three_restatements_of_lists_sort_agree) diffs the three through eh_selftest_sort_by_priority.
 #pragma once

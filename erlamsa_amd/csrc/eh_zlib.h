@@ -14,8 +14,8 @@
 //
 // Execution: ONE lane.  Match finding with lazy evaluation is a chain of data-dependent decisions and the container paths are rare
 // (an input must really be a gzip / zlib / zip file); the wavefront's lane 0 runs these routines as scalar code while the other
-// lanes wait at the next wave_sync().  Checksums over whole buffers (CRC-32, Adler-32) are wave-parallel (below and
-// wave_crc32 in eh_engine.hip).  All state lives in a scratch block the caller hands in (ZDef: 330 KB, ZInf: 3 KB).
+// lanes wait at the next wave_sync().  Checksums over whole buffers (CRC-32, Adler-32) are wave-parallel (below; the
+// checksum pattern of eh_patterns.h uses wave_crc32 too).  All state lives in a scratch block the caller hands in (ZDef: 330 KB, ZInf: 3 KB).
 #pragma once
 #include "eh_device.h"
 

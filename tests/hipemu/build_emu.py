@@ -39,23 +39,31 @@ def build(force=False, race=False):
     return out
 
 
-OUT_HOST_OOM = os.path.join(ROOT, "build", "host_oom")
+def _build_host_program(name, force):
+    """tests/hipemu/<name>.cpp and the engine as one stand-alone program under AddressSanitizer.  -O0: the run is tiny, and the
+    engine compiles in a fraction of the time."""
+    src = os.path.join(ROOT, "erlamsa_amd", "csrc")
+    main = os.path.join(ROOT, "tests", "hipemu", name + ".cpp")
+    out = os.path.join(ROOT, "build", name)
+    deps = [os.path.join(src, f) for f in os.listdir(src)] + [os.path.join(ROOT, "include", "erlamsa_hip.h"),
+                                                                 os.path.join(ROOT, "tests", "hipemu", "hip", "hip_runtime.h"), main]
+    if not force and os.path.exists(out) and all(os.path.getmtime(d) <= os.path.getmtime(out) for d in deps):
+        return out
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    subprocess.check_call(["g++", "-O0", "-g", "-std=c++17", "-ffp-contract=off", "-Wno-attributes", "-fsanitize=address", "-pthread",
+                           "-I", os.path.join(ROOT, "tests", "hipemu"), "-I", os.path.join(ROOT, "include"),
+                           main, "-x", "c++", os.path.join(src, "eh_engine.hip"), "-o", out])
+    return out
 
 
 def build_host_oom(force=False):
-    """host_oom.cpp and the engine as one stand-alone program under AddressSanitizer (see host_oom.cpp).  -O0: the run is tiny,
-    and the engine compiles in a fraction of the time."""
-    src = os.path.join(ROOT, "erlamsa_amd", "csrc")
-    main = os.path.join(ROOT, "tests", "hipemu", "host_oom.cpp")
-    deps = [os.path.join(src, f) for f in os.listdir(src)] + [os.path.join(ROOT, "include", "erlamsa_hip.h"),
-                                                                 os.path.join(ROOT, "tests", "hipemu", "hip", "hip_runtime.h"), main]
-    if not force and os.path.exists(OUT_HOST_OOM) and all(os.path.getmtime(d) <= os.path.getmtime(OUT_HOST_OOM) for d in deps):
-        return OUT_HOST_OOM
-    os.makedirs(os.path.dirname(OUT_HOST_OOM), exist_ok=True)
-    subprocess.check_call(["g++", "-O0", "-g", "-std=c++17", "-ffp-contract=off", "-Wno-attributes", "-fsanitize=address", "-pthread",
-                           "-I", os.path.join(ROOT, "tests", "hipemu"), "-I", os.path.join(ROOT, "include"),
-                           main, "-x", "c++", os.path.join(src, "eh_engine.hip"), "-o", OUT_HOST_OOM])
-    return OUT_HOST_OOM
+    """a context whose device allocations fail (see host_oom.cpp)"""
+    return _build_host_program("host_oom", force)
+
+
+def build_host_lifecycle(force=False):
+    """two contexts that make, and release, every lazily created handle and buffer (see host_lifecycle.cpp)"""
+    return _build_host_program("host_lifecycle", force)
 
 
 OUT_COALESCE_UNIT = os.path.join(ROOT, "build", "coalesce_unit")
@@ -78,5 +86,7 @@ if __name__ == "__main__":
         print(build_coalesce_unit(force="--force" in sys.argv))
     elif "--host-oom" in sys.argv:
         print(build_host_oom(force="--force" in sys.argv))
+    elif "--host-lifecycle" in sys.argv:
+        print(build_host_lifecycle(force="--force" in sys.argv))
     else:
         print(build(force="--force" in sys.argv, race="--race" in sys.argv))

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The device buffers of ONE context through a life in which every one of them grows after a smaller use and is reused unchanged
-after a larger one (erlamsa_amd/csrc/eh_engine.hip, DevBuf): result arrays, slots, both arenas, ordered offsets, bounce buffers,
+after a larger one (erlamsa_amd/csrc/eh_host.h, DevBuf): result arrays, slots, both arenas, ordered offsets, bounce buffers,
 seeds and profile ids, the uniqueness filter's arrays, the selection list, the corpus.  Every result is held against the CPU oracle.
 
   ERLAMSA_HIP_LIB=build/liberlamsa_hip_emu.so python tests/hipemu/emu_buffers.py

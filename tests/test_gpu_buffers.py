@@ -1,4 +1,4 @@
-"""The device buffers of one context on the GPU (csrc/eh_engine.hip, DevBuf): each grows after a smaller use and is reused unchanged
+"""The device buffers of one context on the GPU (csrc/eh_host.h, DevBuf): each grows after a smaller use and is reused unchanged
 after a larger one, and every result equals the CPU oracle's.  The body is the one tests/test_emulated_buffers.py runs on the CPU
 emulator (tests/hipemu/emu_buffers.py)."""
 import os

@@ -1,4 +1,4 @@
-"""Request coalescing from several threads on the GPU (csrc/eh_coalesce.h and the coalescer of csrc/eh_engine.hip): submitters, pollers
+"""Request coalescing from several threads on the GPU (csrc/eh_coalesce.h and the coalescer of csrc/eh_host_coalesce.h): submitters, pollers
 and a flusher share one context, and every ticket gets the bytes its request gets alone, which are the CPU oracle's.  The body is
 the one tests/test_emulated_kernel.py runs on the CPU emulator (tests/hipemu/emu_coalesce_threads.py)."""
 import os
