@@ -467,13 +467,19 @@ __global__ void __launch_bounds__(64) eh_test_zlib_kernel(int op, const uint8_t*
 // Batches in flight on several HIP streams (one context each) only run side by side when every stream gets a hardware queue of its
 // own; the runtime maps streams onto GPU_MAX_HW_QUEUES of them (default 4: with six passes in flight pairs of them serialise,
 // 21.7 instead of 33.7 GB/s, profiles/r04_bench_q4.json).  The variable is read when the HIP runtime initialises, i.e. at the first
-// HIP call of the process: set here, when the library is loaded, unless the host has chosen a value itself.  (A process that has
-// used HIP before it loads this library - a torch that came first - keeps what it started with: INTEGRATION.md section 3.)
+// HIP call of the process: set here, when the library is loaded, unless the host has asked for eight or more itself.  (A process that
+// has used HIP before it loads this library - a torch that came first - keeps what it started with: INTEGRATION.md section 3.)
+#include "eh_host_queues.h"
 __attribute__((constructor)) static void eh_runtime_defaults() {
-  // Only when the variable is not set, and only here - at load time, before this library has made a HIP call.  A host that loads the
-  // library into a process with threads already running (a BEAM: setenv is not safe against a concurrent getenv) exports
-  // GPU_MAX_HW_QUEUES=8 itself before it starts; then nothing is written (note 0).
-  if (!getenv("GPU_MAX_HW_QUEUES")) setenv("GPU_MAX_HW_QUEUES", "8", 0);
+  // The rule is hw_queues_to_write (eh_host_queues.h): eight when the variable is not set or is a plain decimal number below eight -
+  // a 4 in the environment is the runtime's default written out by whoever started the process, and puts seven streams on four
+  // queues -, nothing otherwise: never lowered, nothing above eight, and what is no number is left to the runtime.  Once, and only
+  // here - at load time, before this library has made a HIP call.  A host that loads the library into a process with threads already
+  // running (a BEAM: setenv is not safe against a concurrent getenv) exports GPU_MAX_HW_QUEUES=8 itself before it starts, and a
+  // process where torch initialised HIP first exports it before torch does; both still see no setenv here (INTEGRATION.md section 3,
+  // note 0).
+  const int want = eh::hw_queues_to_write(getenv("GPU_MAX_HW_QUEUES"));
+  if (want) { char v[16]; snprintf(v, sizeof v, "%d", want); setenv("GPU_MAX_HW_QUEUES", v, 1); }
 }
 
 // =============================================================================================
