@@ -104,15 +104,25 @@ def fuzz_batch(inputs, opts=None, return_status=False, device=0):
         raise Unsupported(host_only(opts))
     eng = _engine(device)
     _configure(eng, opts)
+    _seen_set(eng, opts)
+    data, off = pack_corpus(list(inputs))
+    eng.upload_corpus(data, off)
+    eng.fuzz_batch(seed=_seed_of(opts), first_case=int(opts.get("first_case", 1)), n=len(inputs))
+    return _batch_results(eng, opts, return_status)
+
+
+def _seen_set(eng, opts):
+    """opts["fresh"]: the engine keeps a seen set of that capacity (made on first use, kept while the capacity stays the same)"""
     if opts.get("fresh"):
         capacity = int(opts["fresh"])
         if capacity < 1:
             raise ValueError("fresh: the capacity of the seen set, a positive int")
         if eng.seen_count()[1] != capacity:
             eng.seen_reserve(capacity)
-    data, off = pack_corpus(list(inputs))
-    eng.upload_corpus(data, off)
-    eng.fuzz_batch(seed=_seed_of(opts), first_case=int(opts.get("first_case", 1)), n=len(inputs))
+
+
+def _batch_results(eng, opts, return_status):
+    """what fuzz_batch returns for the engine's last batch"""
     if opts.get("fresh"):
         # only the cases that are neither a repeat inside the batch nor an output of an earlier batch cross PCIe
         cls, _, _ = eng.result_seen(commit=True)
@@ -132,6 +142,43 @@ def fuzz_batch(inputs, opts=None, return_status=False, device=0):
     got = dict(zip(reps.tolist(), eng.download_select(reps)))
     outs = [got[int(f)] for f in first_of]
     return (outs, status, first_of) if return_status else outs
+
+
+def fuzz_generations(inputs, opts=None, generations=1, keep="all", return_status=False, device=0):
+    """A generational campaign on the device: generation g is ONE batch over the whole current corpus, and what it keeps becomes the
+    corpus of generation g + 1 without crossing PCIe (Engine.corpus_promote / corpus_promote_fresh, replace mode).  Case numbers
+    continue where the previous generation stopped, as one fuzzer/1 run would count them.
+      keep="all"    every EH_CASE_OK case of non-zero length, in case order: what record_result/2 keeps (erlamsa_main.erl:120-122)
+      keep="fresh"  the cases no earlier case of the campaign's seen set has produced (opts["fresh"]: the set's capacity), none longer
+                    than opts["max_entry_bytes"] (0 or absent: no limit)
+    -> what fuzz_batch returns for the LAST generation that ran (with return_status the statuses, and the classes with "fresh"); the
+    campaign stops early when a generation promotes nothing.  Cases that stopped at an engine limit are never promoted."""
+    opts = dict(opts or {})
+    if host_only(opts):
+        raise Unsupported(host_only(opts))
+    if keep not in ("all", "fresh"):
+        raise ValueError("keep: 'all' or 'fresh'")
+    if keep == "fresh" and not opts.get("fresh"):
+        raise ValueError("keep='fresh' needs opts['fresh'], the capacity of the seen set")
+    if int(generations) < 1:
+        raise ValueError("generations: a positive int")
+    eng = _engine(device)
+    _configure(eng, opts)
+    _seen_set(eng, opts)
+    data, off = pack_corpus(list(inputs))
+    eng.upload_corpus(data, off)
+    seed, first = _seed_of(opts), int(opts.get("first_case", 1))
+    for g in range(int(generations)):
+        n = eng.n_corpus
+        eng.fuzz_batch(seed=seed, first_case=first, n=n)
+        first += n
+        if keep == "fresh":
+            taken, _ = eng.corpus_promote_fresh(max_entry_bytes=int(opts.get("max_entry_bytes", 0)))
+        else:
+            taken, _ = eng.corpus_promote(np.flatnonzero((eng.status() == CASE_OK) & (eng.lens() > 0)))
+        if not taken:
+            break
+    return _batch_results(eng, opts, return_status)
 
 
 class EngineLimit(RuntimeError):

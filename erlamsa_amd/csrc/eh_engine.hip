@@ -43,6 +43,7 @@
 #include "eh_zip.h"
 #include "eh_unique.h"
 #include "eh_seen.h"
+#include "eh_promote.h"
 #include "eh_comm.h"
 #include "eh_coalesce.h"
 
@@ -494,4 +495,5 @@ __attribute__((constructor)) static void eh_runtime_defaults() {
 #include "eh_host_options.h"
 #include "eh_host_unique.h"
 #include "eh_host_seen.h"
+#include "eh_host_promote.h"
 #include "eh_host_selftest.h"

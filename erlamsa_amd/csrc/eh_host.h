@@ -124,6 +124,12 @@ struct SeenState {
     capacity = slots = held = dropped = seq = 0; have = false; committed = false;
   }
 };
+// corpus promotion (eh_promote.h): sized on first use, reused while they fit.  `ent` holds the three entry arrays one behind the other
+// (source offsets, lengths, destinations: `ent_cap` entries each), `elen` a value per case of the batch, `pfirst` a piece number per entry
+struct PromoteState {
+  DevBuf<uint64_t> d_elen, d_ent, d_pfirst; DevBuf<unsigned long long> d_ctr;
+  uint64_t ent_cap = 0;
+};
 
 struct eh_ctx {
   int device = 0;
@@ -145,6 +151,7 @@ struct eh_ctx {
   Downloader dl;
   UniqueState uq;
   SeenState sn;
+  PromoteState pm;
   // request coalescing (eh_submit / eh_flush / eh_poll): the bookkeeping (eh_coalesce.h) and its lock, which a public entry point takes
   // once and no function below it takes again
   Coalescer co; std::mutex co_lock;

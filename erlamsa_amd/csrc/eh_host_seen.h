@@ -123,10 +123,9 @@ int eh_seen_export(eh_ctx* ctx, uint64_t* keys, uint64_t cap_keys, uint64_t* n) 
   HIPCHK(ctx, hipMemcpy(keys, ctx->sn.d_keys, m * 16, hipMemcpyDeviceToHost));
   return EH_OK;
 }
-int eh_result_seen(eh_ctx* ctx, uint32_t commit, uint8_t* cls, uint64_t* n_fresh, uint64_t* fresh_bytes) {
-  if (!ctx) return EH_E_INVALID;
-  std::lock_guard<std::mutex> g(ctx->co_lock); if (int rc = co_idle(ctx)) return rc;
-  if (int rc = sn_need(ctx)) return rc;
+// The last batch's classes in sn.d_cls and its fresh totals (cached by batch_seq); with `commit` the fresh cases' keys are recorded, once
+// per batch.  co_lock held, a set reserved (eh_result_seen, eh_corpus_promote_fresh).
+static int sn_result(eh_ctx* ctx, bool commit) {
   int rc = uq_result(ctx, true); if (rc) return rc;                   // digests, first_of and the flags of the last batch (EH_E_STATE before one)
   const uint64_t n = ctx->res.last_n;
   const bool lookup = ctx->sn.seq != ctx->res.batch_seq;
@@ -138,6 +137,14 @@ int eh_result_seen(eh_ctx* ctx, uint32_t commit, uint8_t* cls, uint64_t* n_fresh
     if (record) ctx->sn.committed = true;
     ctx->sn.seq = ctx->res.batch_seq;
   }
+  return EH_OK;
+}
+int eh_result_seen(eh_ctx* ctx, uint32_t commit, uint8_t* cls, uint64_t* n_fresh, uint64_t* fresh_bytes) {
+  if (!ctx) return EH_E_INVALID;
+  std::lock_guard<std::mutex> g(ctx->co_lock); if (int rc = co_idle(ctx)) return rc;
+  if (int rc = sn_need(ctx)) return rc;
+  int rc = sn_result(ctx, commit != 0); if (rc) return rc;
+  const uint64_t n = ctx->res.last_n;
   if (cls && n) HIPCHK(ctx, hipMemcpy(cls, ctx->sn.d_cls, n, hipMemcpyDeviceToHost));
   if (n_fresh) *n_fresh = ctx->sn.n_fresh;
   if (fresh_bytes) *fresh_bytes = ctx->sn.fresh_bytes;

@@ -39,9 +39,12 @@ ABI_SYMBOLS = [
     "eh_result_digests", "eh_result_unique", "eh_result_download_select", "eh_selftest_unique",
     "eh_profile_add", "eh_profile_count", "eh_fuzz_calls_profiled", "eh_submit_profiled",
     "eh_seen_reserve", "eh_seen_count", "eh_seen_add_keys", "eh_seen_add_corpus", "eh_seen_export", "eh_result_seen", "eh_selftest_seen",
+    "eh_corpus_promote", "eh_corpus_promote_fresh", "eh_corpus_download", "eh_selftest_promote",
 ]
 
 SEEN_FRESH, SEEN_IN_BATCH, SEEN_BEFORE, SEEN_NOT_OK = 0, 1, 2, 3   # cls[i] of eh_result_seen
+
+PROMOTE_REPLACE, PROMOTE_APPEND = 0, 1   # mode of eh_corpus_promote*
 
 MAX_PROFILES = 1024   # EH_MAX_PROFILES
 
@@ -114,6 +117,10 @@ def load_library():
     lib.eh_seen_export.argtypes = [vp, vp, C.c_uint64, u64p]
     lib.eh_result_seen.argtypes = [vp, C.c_uint32, vp, u64p, u64p]
     lib.eh_selftest_seen.argtypes = [vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp]
+    lib.eh_corpus_promote.argtypes = [vp, vp, C.c_uint64, C.c_uint32, u64p, u64p]
+    lib.eh_corpus_promote_fresh.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint32, u64p, u64p]
+    lib.eh_corpus_download.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, u64p]
+    lib.eh_selftest_promote.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, u64p, u64p]
     lib.eh_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
     lib.eh_pool_stats.argtypes = [vp, vp]
     lib.eh_result_summary.argtypes = [vp, vp]
@@ -528,6 +535,54 @@ class Engine:
         cls = np.zeros(max(n, 1), dtype=np.uint8)
         self._chk(self.lib.eh_selftest_seen(self.h, data.ctypes.data, off.ctypes.data, status.ctypes.data, n, 1 if commit else 0, cls.ctypes.data))
         return cls[:n]
+
+    # ---- corpus promotion: outputs of the last batch become seeds on the device (eh_corpus_promote .. eh_selftest_promote)
+    def corpus_promote(self, idx, append=False):
+        """the listed cases of the last batch, in list order, become corpus entries -> (entries, bytes) of the corpus afterwards"""
+        idx = np.ascontiguousarray(idx, dtype=np.uint64).reshape(-1)
+        n, nb = C.c_uint64(), C.c_uint64()
+        self._chk(self.lib.eh_corpus_promote(self.h, idx.ctypes.data, len(idx), PROMOTE_APPEND if append else PROMOTE_REPLACE, C.byref(n), C.byref(nb)))
+        self.n_corpus = n.value
+        return n.value, nb.value
+
+    def corpus_promote_fresh(self, max_entry_bytes=0, max_total_bytes=0, append=False):
+        """the fresh cases of the last batch (as result_seen(commit=True) classifies them), chosen on the device under the two limits
+        (0: none), become corpus entries in case order -> (cases taken, their bytes)"""
+        t, tb = C.c_uint64(), C.c_uint64()
+        self._chk(self.lib.eh_corpus_promote_fresh(self.h, int(max_entry_bytes), int(max_total_bytes), PROMOTE_APPEND if append else PROMOTE_REPLACE,
+                                                   C.byref(t), C.byref(tb)))
+        self.n_corpus = self.corpus_size()[0]
+        return t.value, tb.value
+
+    def corpus_size(self):
+        """-> (entries, bytes) of the corpus the device holds (the size query of eh_corpus_download)"""
+        n, nb = C.c_uint64(), C.c_uint64()
+        self._chk(self.lib.eh_corpus_download(self.h, None, 0, None, 0, C.byref(n), C.byref(nb)))
+        return n.value, nb.value
+
+    def corpus_download(self):
+        """-> (uint8 data[nbytes], uint64 off[n + 1]): the corpus as the device holds it, owned or attached"""
+        n, nb = self.corpus_size()
+        data = np.zeros(max(nb, 1), dtype=np.uint8)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        self._chk(self.lib.eh_corpus_download(self.h, data.ctypes.data, data.size, off.ctypes.data, off.size, None, None))
+        return data[:nb], off
+
+    def selftest_promote(self, data, off, status, cls=None, idx=None, max_entry_bytes=0, max_total_bytes=0, append=False):
+        """the promotion kernels over a caller-made arena (case i = data[off[i]:off[i+1]]): with cls the fresh selection under the two
+        limits, without it the list idx -> (cases taken, their bytes)"""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        status = np.ascontiguousarray(status, dtype=np.int32)
+        n = len(off) - 1
+        cls = None if cls is None else np.ascontiguousarray(cls, dtype=np.uint8)
+        idx = np.ascontiguousarray(idx if idx is not None else [], dtype=np.uint64).reshape(-1)
+        t, tb = C.c_uint64(), C.c_uint64()
+        self._chk(self.lib.eh_selftest_promote(self.h, data.ctypes.data, off.ctypes.data, status.ctypes.data, cls.ctypes.data if cls is not None else None, n,
+                                               idx.ctypes.data, len(idx), int(max_entry_bytes), int(max_total_bytes),
+                                               PROMOTE_APPEND if append else PROMOTE_REPLACE, C.byref(t), C.byref(tb)))
+        self.n_corpus = self.corpus_size()[0]
+        return t.value, tb.value
 
     def download_into(self, host_ptr, cap):
         """Case-ordered outputs of the last batch into caller memory at `host_ptr` (`cap` bytes; pinned or registered

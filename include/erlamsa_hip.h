@@ -413,6 +413,61 @@ int eh_result_seen(eh_ctx* ctx, uint32_t commit, uint8_t* cls, uint64_t* n_fresh
 int eh_selftest_seen(eh_ctx* ctx, const uint8_t* data, const uint64_t* off, const int32_t* status, uint64_t n, uint32_t commit,
                      uint8_t* cls);
 
+/* ---- corpus promotion: outputs of the last batch become corpus entries on the device (added within ABI 8; kernels in
+ * csrc/eh_promote.h).  Reference counterpart: none in erlamsa; it is the step of a generational campaign - take seeds, make cases,
+ * keep the new ones, mutate those - that a feedback loop around a radamsa-style mutator performs on the host.  The filter and the
+ * seen set above say which outputs to keep; these entries write them into the corpus arena, and no kept byte crosses PCIe.
+ *
+ * eh_corpus_promote        the m listed cases of the LAST batch, in list order (repeats allowed, m = 0 allowed), become corpus entries.
+ *                          *n_after / *bytes_after = entries and bytes of the corpus afterwards (each may be NULL).
+ * eh_corpus_promote_fresh  the fresh cases of the last batch, chosen ON THE DEVICE, in case order; no index list crosses PCIe.
+ *                          *taken / *taken_bytes = the promoted cases and the sum of their lengths (each may be NULL).
+ * eh_corpus_download       the corpus as the device holds it, owned or attached: *n entries, *nbytes bytes; with data = NULL or
+ *                          off = NULL only those two (the size query), otherwise data[0 .. *nbytes) and off[0 .. *n] are copied.
+ *                          EH_E_INVALID when cap < *nbytes or cap_entries < *n + 1, EH_E_STATE without a corpus.
+ * eh_selftest_promote      self test hook (tests only), like eh_selftest_unique / eh_selftest_seen: the same kernels over a caller-made
+ *                          arena of n cases.  cls != NULL: the fresh selection with those classes (no seen set is needed or touched);
+ *                          cls = NULL: the explicit list idx[m].  The arena keeps off[0] modulo 64 as its device address modulo 64.
+ *                          No batch is needed; *taken / *taken_bytes as above (m and the list's bytes for a list).
+ * mode: EH_PROMOTE_REPLACE - the promoted entries ARE the corpus afterwards; EH_PROMOTE_APPEND - they follow the entries the
+ *   corpus has (on a context without a corpus that is the same as replace).  Another value is EH_E_INVALID.
+ *
+ * Packed, back to back.  The result is a legal corpus in the sense of eh_corpus_upload: off[i + 1] - off[i] is entry i's length, there
+ *   is no padding - an entry starts at whatever byte address the one before it ends at -, and off[n] is the byte count.  Everything
+ *   that reads a corpus works on it unchanged: eh_fuzz_batch, eh_fuzz_calls*, the file / jump generators that point INTO the arena,
+ *   eh_seen_add_corpus, eh_corpus_device.
+ * Explicit list.  idx[k] >= n of the last batch is EH_E_INVALID.  A listed case whose status is not EH_CASE_OK is EH_E_INVALID, the
+ *   error text names the first such case, and the corpus is unchanged.  An EH_CASE_OK case of length 0 is allowed: an empty seed is
+ *   a legal entry.
+ * Fresh.  Behaves as if eh_result_seen(ctx, 1, ...) had been called for this batch first - the same cache per batch, the same
+ *   idempotence: the promoted outputs are recorded as seen exactly once, and a second call for the same batch promotes the same
+ *   entries.  EH_E_STATE without a seen set.  With len[i] the case's output length,
+ *     eligible(i) = status[i] is EH_CASE_OK and cls[i] is 0 (fresh) and 1 <= len[i] <= max_entry_bytes      (0: no limit)
+ *     S(i)        = the sum of len[j] over the eligible j <= i, in case order
+ *     taken(i)    = eligible(i) and S(i) <= max_total_bytes                                                  (0: no limit)
+ *   The taken cases are therefore a prefix of the eligible ones.  The rule is a scan over the case index: it never depends on
+ *   scheduling, it is decided entirely on the device, and the host reads back two counters.
+ * The last batch's results stay as they are.  The output arena is only read: eh_result_download* after a promotion returns what it
+ *   would have returned before, and so do the filter's and the set's entries.
+ * Ownership.  Replace on a context with an ATTACHED corpus (eh_corpus_attach) leaves the attached arena alone - other contexts share
+ *   it - and gives the context an arena of its own.  Append on an attached corpus first copies it device to device into owned
+ *   buffers.  When the context's own buffers have room, nothing is allocated (the steady state of eh_corpus_upload); otherwise a new
+ *   pair with the same 1.5x room is filled completely and then takes the old pair's place: a failure on the way (EH_E_HIP) leaves the
+ *   corpus that was.  The host's copy of the offsets is made consistent with the device's before the call returns.
+ * Guards, as the filter's entries: EH_E_STATE on a context that has coalesced requests pending or in flight, and (all but
+ *   eh_corpus_download and eh_selftest_promote) before a batch has run.  The last batch has ended and no launch reads the corpus when
+ *   the copy starts.  Offsets and sums are 64-bit throughout; an entry is copied in pieces of EH_UNIQUE_PIECE_BYTES by as many
+ *   wavefronts as it has pieces. */
+#define EH_PROMOTE_REPLACE 0u
+#define EH_PROMOTE_APPEND 1u
+int eh_corpus_promote(eh_ctx* ctx, const uint64_t* idx, uint64_t m, uint32_t mode, uint64_t* n_after, uint64_t* bytes_after);
+int eh_corpus_promote_fresh(eh_ctx* ctx, uint64_t max_entry_bytes, uint64_t max_total_bytes, uint32_t mode, uint64_t* taken,
+                            uint64_t* taken_bytes);
+int eh_corpus_download(eh_ctx* ctx, uint8_t* data, uint64_t cap, uint64_t* off, uint64_t cap_entries, uint64_t* n, uint64_t* nbytes);
+int eh_selftest_promote(eh_ctx* ctx, const uint8_t* data, const uint64_t* off, const int32_t* status, const uint8_t* cls, uint64_t n,
+                        const uint64_t* idx, uint64_t m, uint64_t max_entry_bytes, uint64_t max_total_bytes, uint32_t mode,
+                        uint64_t* taken, uint64_t* taken_bytes);
+
 /* Per-case high-water mark of work memory in bytes (diagnostic; what sizes max_case_bytes and the pool's tiers). */
 int eh_result_peak(eh_ctx* ctx, uint64_t* peak);
 
