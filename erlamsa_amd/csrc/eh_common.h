@@ -1,6 +1,7 @@
 // eh_common.h — ids, tables and plain structs shared by the host API and the
 // device kernels of liberlamsa_hip.so.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 // Everything the kernels read and write besides their registers, the LDS and their stack is HBM (corpus arena, slots, pool areas,
@@ -156,15 +157,153 @@ struct CoJob {
   unsigned long long acc;       // what the chunks add up to (members alive, mismatches found ...)
   uint32_t kind, nchunks, done, pad;
 };
+// indices of CoBoard::stat, in the order eh_coop_stats documents (ABI)
+enum CoStat : int {
+  CO_ST_POSTED = 0,        // jobs posted
+  CO_ST_BY_HELPERS = 1,    // chunks run by helpers ...
+  CO_ST_BY_POSTERS = 2,    // ... and by the posters themselves
+  CO_ST_POSTER_WAIT = 3,   // cycles posters waited for the last chunks
+  CO_ST_BOARD_FULL = 4,    // jobs that found no free entry
+  CO_ST_COUNT = 8,         // words eh_coop_stats hands out (the rest: zero)
+};
 struct CoBoard {
   unsigned long long word[CO_JOBS];
   uint32_t owner[CO_JOBS];      // 1: a poster holds the entry
   uint32_t open;                // entries with chunks to hand out
   uint32_t posters;             // cases under way that have posted a loop: wavefronts whose pass has run out of tickets stay for chunks while there are any
   uint32_t pad[14];
-  unsigned long long stat[8];   // [0] jobs posted, [1] chunks run by helpers, [2] by the posters themselves, [3] cycles posters waited, [4] jobs that found no free entry
+  unsigned long long stat[CO_ST_COUNT];
   CoJob job[CO_JOBS];
 };
+
+// ---- memory the kernels and the host ABI both address by position.  The numbers in the static_asserts are the layout: bench.py, tools/
+// and the callers of eh_result_prof / eh_pool_stats read by word number, so no member may move.
+// EH_PROF slots: BatchCounters::prof[2 * k] and [2 * k + 1] - cycles and calls, or two counts: see the site.  Slots 0 .. M_COUNT - 1 are
+// the mutators' (mux_fuzzers, by MutaId).  The values are what bench.py and tools/ read by number.  Slots with two users, as they stand:
+// 85 and 86 (tree and sgm), 100 .. 103 (the two fuse searches: a call takes one or the other), 112 .. 120 (sgm, and fuse's calls by size).
+enum ProfSlot : int {
+  PROF_B64_LEX = 48,         // b64: lexing, candidates refused, decode, nested call, encode, gather
+  PROF_B64_REFUSED = 49,
+  PROF_B64_DECODE = 50,
+  PROF_B64_NESTED = 51,
+  PROF_B64_ENCODE = 52,
+  PROF_B64_GATHER = 53,
+  PROF_FR_SEARCH = 54,       // fuse on shortened lists (eh_fuse_red.h): the search
+  PROF_FR_MEMBERS = 55,      // ... the node's members found in the original lists
+  PROF_WS_FAILED = 56,       // work memory taken by attempts that failed (mux_fuzzers)
+  PROF_WS_CAND = 57,         // ... the candidates that were used
+  PROF_WS_BESIDES = 58,      // ... what the used attempts took besides their candidate
+  PROF_PAT_PICK_CSUM = 59,   // patterns: pick_csum
+  PROF_PAT_PICK_LEN = 60,    // pick_simple_len
+  PROF_PAT_CS_BLOB = 61,     // cs: the checksummed bytes gathered
+  PROF_PAT_CS_SUM = 62,      // cs: the checksum
+  PROF_PAT_CP_BEGIN = 63,    // cp: pat_container_begin (ar: 78)
+  PROF_PHASE = 64,           // + k: the phases of a case in eh_mutate_kernel (EH_PH(0 .. 3))
+  PROF_SG_BATCH_FAILED = 68, // sgm: failed attempts committed by lane batches
+  PROF_PAT_CP_END = 69,      // cp: the wrapper popped (ar: 79)
+  PROF_TREE = 70,            // + k: eh_tree.h TR_PH / TR_ST, k = 0 .. 7 and 10 .. 15
+  PROF_PAT_AR_BEGIN = 78,
+  PROF_PAT_AR_END = 79,
+  PROF_SG_BATCH_TAGS = 85,   // sgm: tags written by lane batches, batches           (also PROF_TREE + 15: events, parses)
+  PROF_TREE_LANES = 86,      // tree: events decided by lane batches, quotes
+  PROF_SG_TEXT = 86,         // sgm tokenizer: text state + bookkeeping between attempts
+  PROF_SG_TAG_FAILED = 87,   // ... failed attempts
+  PROF_SG_TAG_OK = 88,       // ... accepted tags
+  PROF_SG_PERIOD_LOST = 89,  // sgm replay: gave up, never back in the state a period later
+  PROF_SG_TOKENIZE = 90,     // sgm: sgml_tokenize, sgml_flags, the mutation, the result gathered
+  PROF_SG_FLAGS = 91,
+  PROF_SG_MUTATE = 92,
+  PROF_SG_GATHER = 93,
+  PROF_SG_REPLAY = 94,       // sgm replay: tokens written, replays
+  PROF_SG_STRETCH = 95,      // sgm: stretches found, searches
+  PROF_FB_PASS_N1_LDS = 96,  // fuse, streaming search (eh_fuse2.h): a pass by where its tables are - also 105 .. 107, 110, 111
+  PROF_FR_CUTS = 97,         // fuse on shortened lists: finding + making the cuts, calls that took them
+  PROF_FR_NO_CUT = 98,       // ... calls that found none
+  PROF_SG_NO_REPLAY = 99,    // sgm: checked but not replayed; of them: look-ahead too long
+  PROF_FB_ALLOC = 100,       // fuse, streaming search: a round's steps
+  PROF_FB_BITS0 = 101,
+  PROF_FB_ETEST = 102,
+  PROF_FB_SCAN = 103,
+  PROF_FL_ROUND1 = 100,      // fuse, search in LDS (eh_fuse_lds.h): first round, later rounds, rounds of single members, the choice
+  PROF_FL_ROUNDS = 101,
+  PROF_FL_SINGLE = 102,
+  PROF_FL_SELECT = 103,
+  PROF_FB_CLEAR = 104,
+  PROF_FB_PASS_LDS = 105,
+  PROF_FB_PASS_GLOBAL = 106,
+  PROF_FB_PASS_LAST = 107,
+  PROF_FB_TAIL = 108,
+  PROF_FB_SELECT = 109,
+  PROF_FB_PASS_TEST = 110,
+  PROF_FB_PASS_N1 = 111,
+  PROF_FUSE_BY_SIZE = 112,   // + b: fuse calls by log2(la + lb), b = 0 .. 13
+  PROF_SG_SETUP = 112,       // sgm tokenizer: set-up, after an accepted tag, lane batches, the next '<'
+  PROF_SG_AFTER_ACCEPT = 113,
+  PROF_SG_LANE_BATCHES = 114,
+  PROF_SG_FIND_LT = 115,
+  PROF_SG_NEXT_STOP = 116,   // sgm: building the next-stop table
+  PROF_SG_PHASE1 = 117,      // sgm: the tokenizer's first phase
+  PROF_SG_ATTRS_WALKED = 118,// sgm: attributes an attempt walked
+  PROF_SG_EVENTS = 119,      // sgm: events found, bytes tokenized
+  PROF_SG_ATTRS = 120,       // sgm: attributes written by attribute batches, batches
+  PROF_FUSE_ROUNDS = 126,    // fuse: refinement rounds, calls
+  PROF_WG_START = 127,       // earliest / latest workgroup start of the dispatch (atomicMin / atomicMax, not sums)
+  PROF_SLOTS = 128,
+};
+
+// The counters of a batch (Results::d_counters): zeroed by eh_prologue_kernel, added to by eh_mutate_kernel.
+struct BatchCounters {
+  unsigned long long ticket;        // next case to hand out
+  unsigned long long out_cursor;    // bump cursor of the output arena (KParams::out_cursor)
+  unsigned long long in_bytes;      // (KParams::in_bytes)
+  unsigned long long done;          // cases of the pass that are done (the lingering wavefronts watch it)
+  unsigned long long lingering;     // wavefronts that stayed for posted chunks
+  unsigned long long out_bytes;     // output bytes of the batch
+  unsigned long long left;          // workgroups that have left
+  unsigned long long wg_ticks;      // 100 MHz ticks: the workgroups' lifetimes ...
+  unsigned long long prof[2 * PROF_SLOTS];   // EH_PROF builds (KParams::prof, eh_result_prof)
+  unsigned long long by_status[6];  // cases of the batch by CaseStatus
+  unsigned long long pad0[2];
+  unsigned long long case_ticks;    // ... their time in cases ...
+  unsigned long long linger_ticks;  // ... and lingering for posted chunks
+  unsigned long long pad1[238];
+};
+static_assert(sizeof(BatchCounters) == 4096, "BatchCounters: 512 words");
+static_assert(offsetof(BatchCounters, ticket) == 0 && offsetof(BatchCounters, out_cursor) == 8 && offsetof(BatchCounters, in_bytes) == 16 &&
+              offsetof(BatchCounters, done) == 24 && offsetof(BatchCounters, lingering) == 32 && offsetof(BatchCounters, out_bytes) == 40 &&
+              offsetof(BatchCounters, left) == 48 && offsetof(BatchCounters, wg_ticks) == 56 && offsetof(BatchCounters, prof) == 8 * 8 &&
+              offsetof(BatchCounters, by_status) == 264 * 8 && offsetof(BatchCounters, case_ticks) == 272 * 8 &&
+              offsetof(BatchCounters, linger_ticks) == 273 * 8, "BatchCounters: word numbers");
+
+// The totals of a batch in page-locked host memory (Results::h_sum): the last workgroup of eh_mutate_kernel to leave writes them, `seq`
+// last; eh_result_summary and eh_result_occupancy read them without a copy call.
+struct BatchSummary {
+  unsigned long long unused0;
+  unsigned long long out_bytes;
+  unsigned long long n;
+  unsigned long long by_status[6];
+  unsigned long long seq;           // KParams::batch_seq of the batch the values belong to
+  unsigned long long wg_ticks, case_ticks, linger_ticks, workgroups;   // eh_result_occupancy out[0 .. 3], in this order
+  unsigned long long pad[2];
+};
+static_assert(sizeof(BatchSummary) == 128, "BatchSummary: 16 words");
+static_assert(offsetof(BatchSummary, out_bytes) == 8 && offsetof(BatchSummary, n) == 16 && offsetof(BatchSummary, by_status) == 24 &&
+              offsetof(BatchSummary, seq) == 72 && offsetof(BatchSummary, wg_ticks) == 80 && offsetof(BatchSummary, case_ticks) == 88 &&
+              offsetof(BatchSummary, linger_ticks) == 96 && offsetof(BatchSummary, workgroups) == 104, "BatchSummary: word numbers");
+
+// The counters of the work-area pool (DevPool::d_ctr, KParams::pool_ctr).  Every tier t is a ring of free area indices.  eh_pool_stats
+// copies words [0, 40) out as they are.
+struct PoolCounters {
+  struct { unsigned long long pop, push; } ring[10];   // tickets handed to poppers / pushers of tier t (the device: pool_tickets, eh_device.h)
+  unsigned long long wait_ticks[10];                    // ticks wavefronts waited for an area of tier t
+  unsigned long long waits[10];                         // how many had to wait
+  unsigned long long most_out[10];                      // the most areas of tier t wanted at the same time
+  unsigned long long pad[14];
+};
+static_assert(POOL_TIERS + 1 <= 10, "PoolCounters has ten tiers' room");
+static_assert(sizeof(PoolCounters) == 64 * 8, "PoolCounters: 64 words");
+static_assert(offsetof(PoolCounters, ring) == 0 && sizeof(PoolCounters::ring[0]) == 16 && offsetof(PoolCounters, wait_ticks) == 20 * 8 &&
+              offsetof(PoolCounters, waits) == 30 * 8 && offsetof(PoolCounters, most_out) == 40 * 8, "PoolCounters: word numbers");
 
 struct KParams {
   cbptr corpus;
@@ -194,15 +333,14 @@ struct KParams {
   qptr trace_off;        // EH_FLAG_META_TRACE: where the case's trace sits in `out` ...
   wptr trace_len;        // ... and its length in bytes (TraceKind events, above)
   uint32_t flags;             // EH_FLAG_*
-  EH_G unsigned long long* prof;   // EH_PROF builds: [2*k] cycles, [2*k+1] calls; k < 64 mutator fn, 64.. phases
-  EH_G unsigned long long* ticket;
+  EH_G unsigned long long* prof;   // EH_PROF builds: BatchCounters::prof - [2*k] cycles, [2*k+1] calls of slot k (ProfSlot)
+  EH_G BatchCounters* ctr;          // the batch's counters (out_cursor, in_bytes and prof above point into the same block)
   EH_G unsigned long long* in_bytes;
   // Work areas.  Workgroup w of a batch owns slot w of the context (block tables + work_cap bytes of work area): a slot per
   // launched workgroup, so no wavefront ever waits for one.  A case that outgrows what it holds borrows a larger area from
   // a POOL all contexts of the device share (eh_host.h DevPool, eh_host_pool.h; tiers 1..ntiers, twice the area per tier up to
   // big_case_bytes) and goes on there; only the mutator attempt that ran out of memory is repeated (eh_device.h, ws_regrow).
-  // Every tier is a ring of free area indices: pool_ctr[2t] = pop tickets, pool_ctr[2t+1] = push tickets,
-  // pool_ctr[20+t] = ticks wavefronts waited for an area of tier t, pool_ctr[30+t] = how many had to wait.
+  // Every tier is a ring of free area indices; its tickets and waits are counted in PoolCounters.
   bptr slot_base;
   uint64_t slot_stride;
   int32_t ntiers;                // tiers of the pool (1..ntiers)
@@ -211,9 +349,9 @@ struct KParams {
   uint64_t pool_cap[POOL_TIERS + 1];    // work-area bytes of an area of tier t (pool_cap[0] == work_cap: the slot's own)
   uint32_t pool_cnt[POOL_TIERS + 1];
   wptr pool_ring[POOL_TIERS + 1];
-  EH_G unsigned long long* pool_ctr;
+  EH_G PoolCounters* pool_ctr;
   EH_G CoBoard* board;          // nullptr: every case does all its work itself (EH_FLAG_NO_COOP)
-  EH_G unsigned long long* summary_out;  // page-locked HOST memory: the last workgroup to leave writes the batch's totals there (eh_result_summary reads them without a copy call)
+  EH_G BatchSummary* summary_out;  // page-locked HOST memory: the last workgroup to leave writes the batch's totals there (eh_result_summary reads them without a copy call)
   uint64_t batch_seq;           // ... stamped with this number
   uint32_t co_copy_min, co_copy_chunk;   // bytes: copies / compares of co_copy_min and more are posted in chunks of co_copy_chunk
   uint32_t co_fb_min, co_fb_chunk;       // positions: the same for the streaming passes of eh_fuse2.h (chunk: a multiple of 1024)

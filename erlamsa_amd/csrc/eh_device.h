@@ -300,7 +300,48 @@ EH_DEV bool wave_equal(cbptr a, cbptr b, uint32_t n) {
 constexpr int MAX_CHUNKS = POOL_TIERS + 1;
 constexpr int MAX_NEST = 6;         // nested scheduler calls (b64 / sgm / js inner mutations)
 constexpr int LEX_LEVELS = MAX_NEST + 1;
-constexpr int ST_STATE_WORDS = 84;  // sizeof(StState) / 4 (eh_text.h; checked there)
+
+// ---- a slot: what a workgroup of a batch owns in device memory (KParams::slot_base), the work area behind it.  Definitions only:
+// the code that uses each part is where it was.
+// per-mutator state of lis/lrs (eh_text.h): [Count | Lines], each stored line = optional nested line + plain tail
+struct StLineRef { uint64_t nptr; uint64_t pptr; uint32_t nlen; uint32_t plen; uint32_t has_nested; uint32_t pad; };
+struct StState { int32_t count; int32_t pad[3]; StLineRef ln[10]; };
+constexpr int ST_STATE_WORDS = sizeof(StState) / 4;
+struct FoState { uint64_t ptr; uint32_t len; uint32_t has; };   // the block fo keeps (eh_fuse.h)
+struct PatFrame {           // a sizer/csum wrapper waiting for its inner evaluation (prepare4sizer, eh_patterns.h)
+  int kind;                 // P_SZ or P_CS
+  int em_field;             // sz: index of the length-field piece in the emit list; cs: first inner piece
+  bptr field;           // sz: the Size/8 bytes to fill in
+  uint32_t size_bits, big;  // sz
+  uint64_t tail_ptr; uint32_t tail_len;   // sz: TailBin
+  uint32_t crc;             // cs: 1 crc32, 0 xor8
+};
+// Lex caches (eh_lex.h), one per nesting level of the scheduler: a mutator that walks its block's chunk table may call the
+// scheduler on a piece of it (base64 chunks, inner texts), and the mutators down there lex their own blocks.  A table lives at
+// the top of a work-area chunk and survives candidate discards; tcap = entries it has room for (0: no table).
+struct LexChunk;
+struct LexCache { uint64_t ptr; uint32_t len; int32_t n; EH_G LexChunk* tab; uint32_t tcap; uint32_t pad; };
+// The states a nested scheduler level starts afresh: the waiting level's are parked word by word (MxFrame, MutatorSave) and put back.
+struct NestState { StState st[2]; uint8_t pad[32]; FoState fo; };   // st[0] lis, st[1] lrs
+static_assert(sizeof(NestState) == 720 && offsetof(NestState, st) == 0 && sizeof(StState) == 336 && offsetof(NestState, fo) == 704, "NestState");
+constexpr uint64_t AUX_BYTES = 4096;
+struct SlotAux {            // per-slot mutator and pattern state (Ctx::aux)
+  NestState nest;
+  uint8_t pad0[1152 - sizeof(NestState)];
+  PatFrame frames[MAX_FRAMES];        // run_patterns: the wrapper stack
+  uint8_t pad1[2048 - 1152 - MAX_FRAMES * sizeof(PatFrame)];
+  LexCache lex[LEX_LEVELS];
+  uint8_t pad2[AUX_BYTES - 2048 - LEX_LEVELS * sizeof(LexCache)];
+};
+static_assert(sizeof(SlotAux) == AUX_BYTES && offsetof(SlotAux, nest) == 0 && offsetof(SlotAux, frames) == 1152 && offsetof(SlotAux, lex) == 2048, "SlotAux");
+struct Slot {               // block list, scratch list, emit list, aux, meta-trace bytes; the work area follows
+  Blk bl[MAX_BLOCKS], bl2[MAX_BLOCKS], em[MAX_EMITS];
+  SlotAux aux;
+  uint8_t trace[TRACE_CAP];
+};
+constexpr uint64_t SLOT_TABLE_BYTES = sizeof(Slot);
+static_assert(offsetof(Slot, bl2) == 32768 && offsetof(Slot, em) == 65536 && offsetof(Slot, aux) == 131072 && offsetof(Slot, trace) == 135168 &&
+              sizeof(Slot) == 167936, "Slot");
 #define EH_SET_OVERFLOW(c, site) ((c).ovf_line = (site), (c).ovf_need = 0, (c).ovf_req = 0, (c).status = CASE_OVERFLOW)
 struct MuFrame;
 struct Ctx {
@@ -313,7 +354,7 @@ struct Ctx {
   EH_G Blk* em;
   int nem;
   uint32_t max_block_scaled;   // round(MAX_BLOCK_SIZE * blockscale) of the case's configuration: the context's, or its option profile's
-  bptr aux;        // per-slot mutator state (lis/lrs lines, fo block)
+  EH_G SlotAux* aux;   // per-slot mutator state (lis/lrs lines, fo block), wrapper stack, lex caches
   // linear work allocator
   bptr ws;
   // ws + ws_used is the next free byte; ws_used and ws_cap are VIRTUAL offsets that run on across the chunks of the work
@@ -396,7 +437,7 @@ struct LaneTab {
 };
 enum { R_SAME = 0, R_NEW = 1 };
 
-// EH_PROF builds: cycle counters per code region (eh_result_prof slots; 0..63 mutators, 64.. phases)
+// EH_PROF builds: cycle counters per code region (eh_result_prof; the slots k are ProfSlot, eh_common.h)
 #ifdef EH_PROF
 #define EH_PT0 uint64_t pt_ = __builtin_readcyclecounter()
 #define EH_PT(c, k) do { uint64_t n_ = __builtin_readcyclecounter(); if (EH_LANE == 0) { atomicAdd(&(c).p->prof[2 * (k)], (unsigned long long)(n_ - pt_)); atomicAdd(&(c).p->prof[2 * (k) + 1], 1ull); } pt_ = n_; } while (0)
@@ -460,23 +501,26 @@ EH_DEV void pool_nap() {
   fprintf(stderr, "hipemu: a wait for a pool area can never end with one wavefront running (block %u)\n", blockIdx.x); abort();
 #endif
 }
+// The tickets of tier t by word number: pop at 2t, push at 2t + 1.  (&ring[t].pop is the same address, but computed as t * 16 in 64 bits
+// where this is 2t in 32: other instructions in ws_regrow and ws_release_to.)
+EH_DEV EH_G unsigned long long* pool_tickets(const EH_G KParams& p) { return &p.pool_ctr->ring[0].pop; }
 EH_DEV uint32_t pool_pop(const EH_G KParams& p, int t) {
   uint32_t v = 0xFFFFFFFFu;
   if (EH_LANE == 0) {
-    unsigned long long h = atomicAdd(&p.pool_ctr[2 * t], 1ull);
+    unsigned long long h = atomicAdd(pool_tickets(p) + 2 * t, 1ull);
     wptr e = p.pool_ring[t] + (h % p.pool_cnt[t]);
     v = atomicExch(e, 0xFFFFFFFFu);
     if (v == 0xFFFFFFFFu) {                                          // every area of the tier is out: wait for a push (eh_pool_stats counts the cycles)
       uint64_t w0 = __builtin_readcyclecounter();
       for (;;) { pool_nap(); v = atomicExch(e, 0xFFFFFFFFu); if (v != 0xFFFFFFFFu) break; }
-      atomicAdd(&p.pool_ctr[20 + t], (unsigned long long)(__builtin_readcyclecounter() - w0));
-      atomicAdd(&p.pool_ctr[30 + t], 1ull);
+      atomicAdd(&p.pool_ctr->wait_ticks[t], (unsigned long long)(__builtin_readcyclecounter() - w0));
+      atomicAdd(&p.pool_ctr->waits[t], 1ull);
     }
     // the most areas of the tier wanted at the same time (eh_pool_stats): what says how to split the pool's memory over the tiers
     // (holders + wavefronts waiting for one, so it can exceed the tier's size)
-    unsigned long long back = atomicAdd(&p.pool_ctr[2 * t + 1], 0ull);
+    unsigned long long back = atomicAdd(pool_tickets(p) + 2 * t + 1, 0ull);
     unsigned long long outn = h + 1 + p.pool_cnt[t] > back ? h + 1 + p.pool_cnt[t] - back : 0;
-    atomicMax(&p.pool_ctr[40 + t], outn);
+    atomicMax(&p.pool_ctr->most_out[t], outn);
   }
 #ifndef EH_NO_POOL_FENCE
   __threadfence();                                                   // the previous owner's stores (another XCD's L2) are behind us
@@ -488,7 +532,7 @@ EH_DEV void pool_push(const EH_G KParams& p, int t, uint32_t v) {
   __threadfence();                                                   // our stores to the area are written back before it changes hands
 #endif
   if (EH_LANE == 0) {
-    unsigned long long h = atomicAdd(&p.pool_ctr[2 * t + 1], 1ull);
+    unsigned long long h = atomicAdd(pool_tickets(p) + 2 * t + 1, 1ull);
     wptr e = p.pool_ring[t] + (h % p.pool_cnt[t]);
     while (atomicCAS(e, 0xFFFFFFFFu, v) != 0xFFFFFFFFu) pool_nap();
   }
@@ -535,7 +579,7 @@ __device__ __noinline__ bool co_run(uint32_t kind, uint32_t nchunks, CoArgs args
   if (l == 0) {
     const uint32_t h = (blockIdx.x * 2654435761u) >> 26;
     for (uint32_t k = 0; k < 4 && slot == CO_JOBS; k++) { const uint32_t s = (h + 17u * k) & (CO_JOBS - 1); if (atomicCAS(&bd->owner[s], 0u, 1u) == 0u) slot = s; }
-    if (slot == CO_JOBS) atomicAdd(&bd->stat[4], 1ull);
+    if (slot == CO_JOBS) atomicAdd(&bd->stat[CO_ST_BOARD_FULL], 1ull);
   }
   slot = uni(slot);
   if (slot == CO_JOBS) return false;
@@ -553,7 +597,7 @@ __device__ __noinline__ bool co_run(uint32_t kind, uint32_t nchunks, CoArgs args
     gen = ((co_ld64(&bd->word[slot]) >> 32) + 1ull) | 1ull;                 // (closed words carry even generations)
     atomicExch(&bd->word[slot], gen << 32);
     atomicAdd(&bd->open, 1u);
-    atomicAdd(&bd->stat[0], 1ull);
+    atomicAdd(&bd->stat[CO_ST_POSTED], 1ull);
   }
   c.co_posted = 1;
   uint32_t mine = 0;
@@ -574,8 +618,8 @@ __device__ __noinline__ bool co_run(uint32_t kind, uint32_t nchunks, CoArgs args
     atomicAdd(&bd->open, 0xFFFFFFFFu);                                       // (- 1)
     atomicExch(&bd->word[slot], (gen + 1ull) << 32);                        // closed: a chunk number drawn from here on belongs to no job
     sum = co_ld64(&j->acc);
-    atomicAdd(&bd->stat[2], (unsigned long long)mine);
-    atomicAdd(&bd->stat[3], (unsigned long long)(__builtin_readcyclecounter() - w0));
+    atomicAdd(&bd->stat[CO_ST_BY_POSTERS], (unsigned long long)mine);
+    atomicAdd(&bd->stat[CO_ST_POSTER_WAIT], (unsigned long long)(__builtin_readcyclecounter() - w0));
   }
   sum = uni64(sum);
   co_acquire();                                                            // what the helpers wrote (they released it) is read from memory, not from this CU's L1
@@ -609,7 +653,7 @@ __device__ __noinline__ void co_help(EH_G CoBoard* bd, uint32_t most) {
     ran++;
     wave_sync();
     co_release();
-    if (l == 0) { atomicAdd(&bd->job[s].done, 1u); atomicAdd(&bd->stat[1], 1ull); }
+    if (l == 0) { atomicAdd(&bd->job[s].done, 1u); atomicAdd(&bd->stat[CO_ST_BY_HELPERS], 1ull); }
   }
 }
 __device__ __noinline__ void co_copy(bptr dst, cbptr src, uint32_t n) {
@@ -631,16 +675,7 @@ __device__ __noinline__ bool co_equal(cbptr x, cbptr y, uint32_t n) {
   return ne == 0;
 }
 
-// Lex caches (eh_lex.h), one per nesting level of the scheduler: a mutator that walks its block's chunk table may call the
-// scheduler on a piece of it (base64 chunks, inner texts), and the mutators down there lex their own blocks.  A table lives at
-// the top of a work-area chunk and survives candidate discards; tcap = entries it has room for (0: no table).
-struct LexChunk;
-struct LexCache { uint64_t ptr; uint32_t len; int32_t n; EH_G LexChunk* tab; uint32_t tcap; uint32_t pad; };
-constexpr uint32_t AUX_LEXCACHE = 2048;                              // offset in Ctx::aux of LexCache[LEX_LEVELS]
-constexpr uint64_t AUX_BYTES = 4096;
-// a slot: block list, scratch list, emit list, aux, meta-trace bytes, then the work area
-constexpr uint64_t SLOT_TABLE_BYTES = (uint64_t)(2 * MAX_BLOCKS + MAX_EMITS) * sizeof(Blk) + AUX_BYTES + TRACE_CAP;
-EH_DEV EH_G LexCache& lex_slot(Ctx& c) { return ((EH_G LexCache*)(c.aux + AUX_LEXCACHE))[c.depth]; }
+EH_DEV EH_G LexCache& lex_slot(Ctx& c) { return c.aux->lex[c.depth]; }   // the lex cache of the nesting level in hand (SlotAux)
 // Work memory at virtual offsets >= v0 is about to be reused: a lexed block that lives there (a decoded base64 chunk, an
 // inner text — temporaries of a mutator attempt) is gone, and the cache is keyed by address.  Only this level's key can
 // be up there: the blocks of the levels above are older than anything the running attempt allocated.
@@ -700,7 +735,7 @@ __device__ __noinline__ void ws_release_to(Ctx&, uint64_t mark) {
     const EH_G KParams& p = *c.p;
     bptr lo = c.ch_base[k] + c.ch_vstart[k]; bptr hi = lo + p.pool_cap[c.ch_tier[k]];
     for (int d = 0; d < LEX_LEVELS; d++) {                           // lex tables and lexed blocks inside the chunk: forget them
-      EH_G LexCache* lc = (EH_G LexCache*)(c.aux + AUX_LEXCACHE) + d;
+      EH_G LexCache* lc = c.aux->lex + d;
       uint64_t tab = uni64((uint64_t)lc->tab), key = c.lex_ptr[d];
       bool tin = uni(lc->tcap) != 0 && tab >= (uint64_t)lo && tab < (uint64_t)hi, kin = key >= (uint64_t)lo && key < (uint64_t)hi;
       if (tin || kin) { c.lex_ptr[d] = 0; if (EH_LANE == 0) { lc->n = -1; if (tin) lc->tcap = 0; } }
@@ -1125,14 +1160,13 @@ EH_DEV void own_meta(Ctx& c, uint32_t fn, int delta, uint32_t hlen) { if (__buil
 // in a MuFrame in work memory and sets call_req; the scheduler below parks the level it is at in an MxFrame, runs the nested level
 // in the same loop, and calls the mutator again with mu_phase = 1 and call_nres = the number of result blocks (at c.bl[c.nb ..),
 // or -1 with the status set).  The call graph has no cycle and the kernel's stack is what the assembler adds up.
-constexpr uint32_t NEST_SAVE = 720;                                          // StState x 2 + FoState (aux + 0 .. 720)
 struct MuFrame {                // a nesting mutator's locals across its nested runs + the table it wants run (v[23]: the MxFrame its nested runs park the level in)
   uint64_t v[24];
   uint32_t pri[64], meta[64];
 };
 struct MxFrame {                // a level of the scheduler that waits for a nested one
   uint32_t e_pri[64], e_meta[64], rank[64];
-  uint32_t aux_save[NEST_SAVE / 4];   // lis / lrs / fo of the waiting level (aux + 0 .. 720): the nested table starts from fresh ones
+  uint32_t aux_save[sizeof(NestState) / 4];   // lis / lrs / fo of the waiting level (SlotAux::nest): the nested table starts from fresh ones
   uint32_t state[64];                 // MxState as it was (eh_device.h g_mx)
 };
 
@@ -1207,7 +1241,7 @@ __device__ __noinline__ void mux_fuzzers(Ctx&, LaneTab& lt) {             // (ON
       // has borrowed a larger area (ws_regrow).  lis / lrs update their store before they allocate: it is put back as well.
       m.rng0 = c.rng; m.work0 = c.work; m.ntrace0 = c.ntrace;
       m.stateful = m.fn == M_LIS || m.fn == M_LRS;
-      if (m.stateful) { cwptr ax = (cwptr)c.aux + (m.fn == M_LRS ? ST_STATE_WORDS : 0); for (int i = l; i < ST_STATE_WORDS; i += 64) g_st_save[i] = ax[i]; }
+      if (m.stateful) { cwptr ax = (cwptr)c.aux->nest.st + (m.fn == M_LRS ? ST_STATE_WORDS : 0); for (int i = l; i < ST_STATE_WORDS; i += 64) g_st_save[i] = ax[i]; }
       m.last_tier = 0;
       c.mu_phase = 0; c.mu = nullptr;
       st = S_RUN;
@@ -1228,14 +1262,13 @@ __device__ __noinline__ void mux_fuzzers(Ctx&, LaneTab& lt) {             // (ON
         if (f) {
           EH_G uint32_t* save = f->aux_save;
           f->e_pri[l] = e_pri; f->e_meta[l] = e_meta; f->rank[l] = rank;
-          EH_G uint32_t* ax = (EH_G uint32_t*)c.aux;
-          for (uint32_t i = l; i < NEST_SAVE / 4; i += 64) save[i] = ax[i];
+          EH_G uint32_t* ax = (EH_G uint32_t*)&c.aux->nest;
+          for (uint32_t i = l; i < (uint32_t)(sizeof(NestState) / 4); i += 64) save[i] = ax[i];
           m.up = (uint64_t)up; m.mu = (uint64_t)c.mu; m.lastm0 = c.lastm; m.tr_base0 = c.tr_base; m.cur0 = c.cur; m.nb0 = c.nb; m.nfs0 = c.nfs;
           lanes_sync();
           if ((uint32_t)l < sizeof(MxState) / 4) f->state[l] = ((const uint32_t*)&m)[l];
           wave_sync();
-          // (StState[0].count, StState[1].count, FoState::has: eh_text.h, eh_fuse.h - the same offsets the reclaim test below reads)
-          if (l == 0) { ((EH_G int32_t*)c.aux)[0] = 0; ((EH_G int32_t*)(c.aux + 4 * ST_STATE_WORDS))[0] = 0; ((EH_G uint32_t*)(c.aux + 704))[3] = 0; }
+          if (l == 0) { c.aux->nest.st[0].count = 0; c.aux->nest.st[1].count = 0; c.aux->nest.fo.has = 0; }
           const int nb0 = c.nb;
           blk_store(c.bl, nb0, c.call_bin, c.call_len);
           e_pri = c.mu->pri[l]; e_meta = c.mu->meta[l];                        // the nested table, lane i = list position i
@@ -1256,7 +1289,7 @@ __device__ __noinline__ void mux_fuzzers(Ctx&, LaneTab& lt) {             // (ON
           lex_forget_from(c, m.mark);
           c.rng = m.rng0; c.work = m.work0; c.ntrace = m.ntrace0;
           c.r_kind = R_SAME; c.r_flush = 0; c.r_drop_next = 0; c.r_changed = 0; c.r2 = 0;
-          if (m.stateful) { lanes_sync(); wptr ax = (wptr)c.aux + (m.fn == M_LRS ? ST_STATE_WORDS : 0); for (int i = l; i < ST_STATE_WORDS; i += 64) ax[i] = g_st_save[i]; }
+          if (m.stateful) { lanes_sync(); wptr ax = (wptr)c.aux->nest.st + (m.fn == M_LRS ? ST_STATE_WORDS : 0); for (int i = l; i < ST_STATE_WORDS; i += 64) ax[i] = g_st_save[i]; }
           wave_sync();
           c.mu_phase = 0; c.mu = nullptr;
           continue;                                                            // (st == S_RUN: the same attempt once more)
@@ -1287,8 +1320,8 @@ __device__ __noinline__ void mux_fuzzers(Ctx&, LaneTab& lt) {             // (ON
     // that were used, 58 what the used attempts took besides their candidate (eh_result_prof; the write traffic's breakdown)
     if (l == 0) {
       const unsigned long long took = c.ws_used > m.mark ? c.ws_used - m.mark : 0ull, cand = c.r_kind == R_NEW ? c.r_len : 0u;
-      if (changed) { atomicAdd(&c.p->prof[2 * 57], cand); atomicAdd(&c.p->prof[2 * 57 + 1], 1ull); atomicAdd(&c.p->prof[2 * 58], took > cand ? took - cand : 0ull); atomicAdd(&c.p->prof[2 * 58 + 1], 1ull); }
-      else { atomicAdd(&c.p->prof[2 * 56], took); atomicAdd(&c.p->prof[2 * 56 + 1], 1ull); }
+      if (changed) { atomicAdd(&c.p->prof[2 * PROF_WS_CAND], cand); atomicAdd(&c.p->prof[2 * PROF_WS_CAND + 1], 1ull); atomicAdd(&c.p->prof[2 * PROF_WS_BESIDES], took > cand ? took - cand : 0ull); atomicAdd(&c.p->prof[2 * PROF_WS_BESIDES + 1], 1ull); }
+      else { atomicAdd(&c.p->prof[2 * PROF_WS_FAILED], took); atomicAdd(&c.p->prof[2 * PROF_WS_FAILED + 1], 1ull); }
     }
 #endif
       own_meta(c, m.fn, m.delta, m.h0.len);                                                // the mutator's own entry is in the Meta it returns, used or failed
@@ -1335,7 +1368,7 @@ __device__ __noinline__ void mux_fuzzers(Ctx&, LaneTab& lt) {             // (ON
       if (m.mark >= vs && c.ws_used - vs > (c.ws_cap - vs) / 8 && c.r_len <= (4u << 20) && !c.r2 && c.r_ptr >= lo && c.r_ptr + c.r_len <= c.ws + c.ws_used) {
         bptr dst = lo;
         bptr hp = (bptr)m.h0.ptr;
-        bool state_refs = uni(((cwptr)c.aux)[0]) != 0 || uni(((cwptr)(c.aux + 336))[0]) != 0 || uni(((cwptr)(c.aux + 704))[3]) != 0;
+        bool state_refs = uni((uint32_t)c.aux->nest.st[0].count) != 0 || uni((uint32_t)c.aux->nest.st[1].count) != 0 || uni(c.aux->nest.fo.has) != 0;
         if (!state_refs && hp >= c.ws + vs && hp + ((m.h0.len + 15u) & ~15u) == lo && ((uintptr_t)hp & 15) == 0) dst = hp;
         if (dst != c.r_ptr) { wave_sync(); wave_move_down(dst, c.r_ptr, c.r_len); wave_sync(); c.r_ptr = dst; }   // candidate stores must have landed
         c.ws_used = (uint64_t)(dst - c.ws) + (((uint64_t)c.r_len + 15) & ~(uint64_t)15);
@@ -1373,8 +1406,8 @@ __device__ __noinline__ void mux_fuzzers(Ctx&, LaneTab& lt) {             // (ON
       c.depth--;
       const int nres = c.nb - c.cur;
       wave_sync();
-      EH_G uint32_t* ax = (EH_G uint32_t*)c.aux; const EH_G uint32_t* save = f->aux_save;
-      for (uint32_t i = l; i < NEST_SAVE / 4; i += 64) ax[i] = save[i];
+      EH_G uint32_t* ax = (EH_G uint32_t*)&c.aux->nest; const EH_G uint32_t* save = f->aux_save;
+      for (uint32_t i = l; i < (uint32_t)(sizeof(NestState) / 4); i += 64) ax[i] = save[i];
       lanes_sync();
 #ifdef HIPEMU
       for (uint32_t k = 0; k < sizeof(MxState) / 4; k++) ((uint32_t*)&m)[k] = f->state[k];   // (the emulator keeps a copy of the LDS per lane)

@@ -200,7 +200,7 @@ __device__ __noinline__ int muta_b64(Ctx&, EH_G LexCache& lc) {
   if (!resume) {
     n = lex_cached(c, lc, H, L, &tab);
     if (n < 0) return 0;
-    EH_PT(c, 48);                                                // eh_result_prof 48..53: lexing, candidates refused, decode, nested call, encode, gather
+    EH_PT(c, PROF_B64_LEX);                                                // eh_result_prof 48..53: lexing, candidates refused, decode, nested call, encode, gather
     snand_mask = rng_rand(c.rng, 3); (void)rng_rand(c.rng, 1);   // mutations([]) :661 -> :1313-1314
   } else {
     tab = (EH_G LexChunk*)uni64(mu->v[0]); n = (int)uni((uint32_t)mu->v[1]); base = (int)uni((uint32_t)mu->v[2]); cand = uni64(mu->v[3]);
@@ -230,10 +230,10 @@ __device__ __noinline__ int muta_b64(Ctx&, EH_G LexCache& lc) {
       bptr dec = ws_alloc(c, (uint64_t)dl + 16);
       bptr pack = nalpha != span ? ws_alloc(c, (uint64_t)nalpha + 16) : nullptr;
       if (!dec || (nalpha != span && !pack)) return 0;
-      EH_PT(c, 49);
+      EH_PT(c, PROF_B64_REFUSED);
       b64_decode_wave(H + a, span, nalpha, dec, pack);
       wave_sync();
-      EH_PT(c, 50);
+      EH_PT(c, PROF_B64_DECODE);
       d = rng_delta(c.rng);                                        // :666
       tr_ai(c, AT_base64_mutator, d);                              // [AddedMeta, {base64_mutator, D} | MAcc] :674: D's entry, then what the nested run adds
       // mutators_mutator(MutasList, []) :667: rand(10) per table entry in table order, each prepended
@@ -254,7 +254,7 @@ __device__ __noinline__ int muta_b64(Ctx&, EH_G LexCache& lc) {
     resume = false;
     const int nres = c.call_nres;
     if (nres < 0) return 0;
-    EH_PT(c, 51);
+    EH_PT(c, PROF_B64_NESTED);
     // NewBin = iolist_to_binary(NewLl) :669
     uint64_t tot = 0;
     for (int k = 0; k < nres; k++) tot += blk_load(c.bl, c.nb + k).len;
@@ -271,10 +271,10 @@ __device__ __noinline__ int muta_b64(Ctx&, EH_G LexCache& lc) {
     piece_put(out, nout, enc, (uint32_t)((tot + 2) / 3 * 4)); nout++;
     done_to = b;
     dacc += d;
-    EH_PT(c, 52);
+    EH_PT(c, PROF_B64_ENCODE);
    }
   }
-  EH_PT(c, 49);
+  EH_PT(c, PROF_B64_REFUSED);
   if (!out) return -1;                                           // nothing decoded: unlex(lex(H)) =:= H
   piece_put(out, nout, H + done_to, L - done_to); nout++;
   wave_sync();
@@ -284,7 +284,7 @@ __device__ __noinline__ int muta_b64(Ctx&, EH_G LexCache& lc) {
   if (!dst) return 0;
   wave_gather(dst, out, nout);
   wave_sync();
-  EH_PT(c, 53);
+  EH_PT(c, PROF_B64_GATHER);
   c.r_kind = R_NEW; c.r_ptr = dst; c.r_len = (uint32_t)total;
   return dacc;
 }

@@ -52,7 +52,7 @@ namespace eh {
 
 EH_DEV int run_mutator_ext(Ctx& c, uint32_t fn, uint32_t mask) {
   (void)mask;
-  EH_G StState* st = (EH_G StState*)c.aux;
+  EH_G StState* st = c.aux->nest.st;
   switch (fn) {
     case M_LD: case M_LDS: case M_LR2: case M_LRI: case M_LR: case M_LS: case M_LP: return muta_line(c, (int)fn);
     case M_LIS: return muta_st_line(c, (int)fn, st);
@@ -63,7 +63,7 @@ EH_DEV int run_mutator_ext(Ctx& c, uint32_t fn, uint32_t mask) {
     case M_B64: return muta_b64(c, lex_slot(c));
     case M_ZIP: return muta_zip(c);
     case M_LEN: return muta_len(c);
-    case M_FT: case M_FN: case M_FO: return muta_fuse(c, (int)fn, (EH_G FoState*)(c.aux + 704));
+    case M_FT: case M_FN: case M_FO: return muta_fuse(c, (int)fn, &c.aux->nest.fo);
     case M_TR2: case M_TD: case M_TS1: case M_TS2: case M_TR: return muta_tree(c, (int)fn);
     case M_SGM: return muta_sgml(c);
     case M_JS: return muta_json(c);
@@ -130,12 +130,12 @@ EH_DEV int choose_pattern(const Pats& t, Rng& rng) {
 // next free slot like any other workgroup of the batch (the old eh_setup_kernel: 29 us on average in the same trace).
 __global__ void __launch_bounds__(64) eh_prologue_kernel(KParams p, int64_t s1, int64_t s2, int64_t s3, RunState* out_, KParams* params_out_,
                                                          unsigned long long* counters_) {
-  // (kernel arguments are what the host passes: generic pointers)
-  EH_G RunState* out = (EH_G RunState*)out_; EH_G KParams* params_out = (EH_G KParams*)params_out_; EH_G unsigned long long* counters = (EH_G unsigned long long*)counters_;
+  // (kernel arguments are what the host passes: generic pointers; counters_ is a BatchCounters, handed over as the words it is zeroed by)
+  EH_G RunState* out = (EH_G RunState*)out_; EH_G KParams* params_out = (EH_G KParams*)params_out_; EH_G BatchCounters* counters = (EH_G BatchCounters*)counters_;
   const int l = EH_LANE;
-  for (int i = l; i < 512; i += 64) counters[i] = 0;             // ticket, output cursor, input bytes, prof slots: 4096 bytes
+  for (int i = l; i < (int)(sizeof(BatchCounters) / 8); i += 64) ((EH_G unsigned long long*)counters)[i] = 0;   // every word of the batch's counters
 #ifdef EH_PROF
-  if (l == 0) counters[8 + 2 * 127] = ~0ull;                     // earliest workgroup start: atomicMin
+  if (l == 0) counters->prof[2 * PROF_WG_START] = ~0ull;         // earliest workgroup start: atomicMin
 #endif
   static_assert(sizeof(KParams) % 4 == 0, "KParams is copied word by word");
   cwptr src = (cwptr)&p;
@@ -178,8 +178,6 @@ EH_DEV void sys_store(EH_G unsigned long long* p, unsigned long long v) {   // a
   __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 #endif
 }
-constexpr int CTR_OCC = 272;                 // counters [272, 274): 100 MHz ticks of the workgroups in cases, lingering for posted chunks ([7]: their lifetimes)
-constexpr int CTR_STATUS = 264;              // counters [264, 270): cases of the batch by status ([8, 264) are the EH_PROF slots)
 constexpr unsigned int CO_LINGER = 24;       // wavefronts of a pass that stay for posted chunks once the pass is out of tickets
 // 2 wavefronts per SIMD = up to 256 VGPRs: at 4 (128 VGPRs) the scheduler loops and the candidate loop of base64_mutator
 // reload spilled registers from scratch on every iteration (7.5 M instead of 1.6 M memory instructions for one
@@ -199,17 +197,17 @@ __global__ void __launch_bounds__(64, EH_WAVES_PER_SIMD) eh_mutate_kernel(const 
   c.work_budget = p.work_budget;
 #ifdef EH_PROF
   // how many workgroups the device holds at once: earliest / latest workgroup start of the dispatch (100 MHz wall clock)
-  if (l == 0) { unsigned long long t = __builtin_amdgcn_s_memrealtime(); atomicMin(&pp->prof[2 * 127], t ? t : 1ull); atomicMax(&pp->prof[2 * 127 + 1], t); }
+  if (l == 0) { unsigned long long t = __builtin_amdgcn_s_memrealtime(); atomicMin(&pp->prof[2 * PROF_WG_START], t ? t : 1ull); atomicMax(&pp->prof[2 * PROF_WG_START + 1], t); }
 #endif
   // this workgroup's slot: block tables + work area
   const uint32_t slot_id = blockIdx.x;
-  bptr slot = p.slot_base + (uint64_t)slot_id * p.slot_stride;
-  c.bl = (EH_G Blk*)slot;
-  c.bl2 = c.bl + MAX_BLOCKS;
-  c.em = c.bl2 + MAX_BLOCKS;
-  c.aux = (bptr)(c.em + MAX_EMITS);
-  bptr const trace0 = c.aux + AUX_BYTES;
-  bptr const ws0 = trace0 + TRACE_CAP;
+  EH_G Slot* slot = (EH_G Slot*)(p.slot_base + (uint64_t)slot_id * p.slot_stride);
+  c.bl = slot->bl;
+  c.bl2 = slot->bl2;
+  c.em = slot->em;
+  c.aux = &slot->aux;
+  bptr const trace0 = slot->trace;
+  bptr const ws0 = (bptr)(slot + 1);
 
   // mode 0: the run state is shared by all cases
   Rng parent; int gen0 = 0; uint32_t pri0 = 0, meta0 = 0; int nfs0 = 0;
@@ -232,7 +230,7 @@ __global__ void __launch_bounds__(64, EH_WAVES_PER_SIMD) eh_mutate_kernel(const 
   while (true) {
     if (tk_next == tk_end) {
       unsigned long long t = 0;
-      if (l == 0) t = atomicAdd(p.ticket, (unsigned long long)TICKET_BATCH);
+      if (l == 0) t = atomicAdd(&p.ctr->ticket, (unsigned long long)TICKET_BATCH);
       tk_next = uni64(t); tk_end = tk_next + TICKET_BATCH;
     }
     if (p.board && uni(co_ld32(&p.board->open)) != 0) co_help(p.board, 2);   // chunks of heavy cases' loops, between two cases of my own
@@ -244,12 +242,12 @@ __global__ void __launch_bounds__(64, EH_WAVES_PER_SIMD) eh_mutate_kernel(const 
       // cases under way and some case on the device is posting; the others leave their slots to the workgroups of the next passes.
       if (p.board) {
         unsigned int mine = p.co_linger;
-        if (l == 0) mine = (unsigned int)atomicAdd(p.ticket + 4, 1ull);
+        if (l == 0) mine = (unsigned int)atomicAdd(&p.ctr->lingering, 1ull);
         if (uni(mine) < p.co_linger) {
           const unsigned long long lg0 = __builtin_amdgcn_s_memrealtime();
           EH_G CoBoard* bd = p.board;
           for (uint32_t spins = 0; spins < (1u << 24); spins++) {
-            if (uni64(co_ld64(p.ticket + 3)) >= p.n || uni(co_ld32(&bd->posters)) == 0) break;
+            if (uni64(co_ld64(&p.ctr->done)) >= p.n || uni(co_ld32(&bd->posters)) == 0) break;
             if (uni(co_ld32(&bd->open)) != 0) co_help(bd, 8);
             else { for (int z = 0; z < 6; z++) __builtin_amdgcn_s_sleep(127); }   // ~20 us: posted loops last hundreds (every poll is a trip to the L2 of all these wavefronts)
           }
@@ -276,7 +274,7 @@ __global__ void __launch_bounds__(64, EH_WAVES_PER_SIMD) eh_mutate_kernel(const 
     c.work = 0; c.depth = 0;
     c.status = CASE_OK; c.lastm = -1; c.nb = 0; c.cur = 0; c.nem = 0; c.ws_used = 0;
     c.r_kind = R_SAME; c.r_flush = 0; c.r_drop_next = 0; c.r2 = 0;
-    if (l == 0) { ((EH_G StState*)c.aux)[0].count = 0; ((EH_G StState*)c.aux)[1].count = 0; for (int d = 0; d < LEX_LEVELS; d++) { EH_G LexCache& lc = ((EH_G LexCache*)(c.aux + AUX_LEXCACHE))[d]; lc.n = -1; lc.tcap = 0; } ((EH_G FoState*)(c.aux + 704))->has = 0; }
+    if (l == 0) { c.aux->nest.st[0].count = 0; c.aux->nest.st[1].count = 0; for (int d = 0; d < LEX_LEVELS; d++) { EH_G LexCache& lc = c.aux->lex[d]; lc.n = -1; lc.tcap = 0; } c.aux->nest.fo.has = 0; }
     wave_sync();
     int gen;
     Rng pr;
@@ -297,7 +295,7 @@ __global__ void __launch_bounds__(64, EH_WAVES_PER_SIMD) eh_mutate_kernel(const 
       setup_run(sel, p.cfg, p.seeds[3 * i], p.seeds[3 * i + 1], p.seeds[3 * i + 2], pr, gen, mask, lt.e_pri, lt.e_meta, c.nfs);
     }
 #ifdef EH_PROF
-#define EH_PH(k) do { uint64_t now_ = __builtin_readcyclecounter(); if (l == 0) { atomicAdd(&p.prof[2 * (64 + (k))], (unsigned long long)(now_ - ph0)); atomicAdd(&p.prof[2 * (64 + (k)) + 1], 1ull); } ph0 = now_; } while (0)
+#define EH_PH(k) do { uint64_t now_ = __builtin_readcyclecounter(); if (l == 0) { atomicAdd(&p.prof[2 * (PROF_PHASE + (k))], (unsigned long long)(now_ - ph0)); atomicAdd(&p.prof[2 * (PROF_PHASE + (k)) + 1], 1ull); } ph0 = now_; } while (0)
     uint64_t ph0 = __builtin_readcyclecounter();
 #else
 #define EH_PH(k) do {} while (0)
@@ -351,9 +349,9 @@ __global__ void __launch_bounds__(64, EH_WAVES_PER_SIMD) eh_mutate_kernel(const 
 #endif
     if (c.co_posted && l == 0) atomicAdd(&p.board->posters, 0xFFFFFFFFu);   // (- 1)
     if (l == 0) {
-      atomicAdd(p.ticket + 3, 1ull);                                        // cases of the pass that are done (the lingering wavefronts watch it)
-      atomicAdd(p.ticket + 5, (unsigned long long)total);                   // the batch's totals on the device (eh_result_summary: one small copy instead of n lengths and n statuses)
-      atomicAdd(p.ticket + CTR_STATUS + (c.status >= 0 && c.status < 6 ? c.status : 1), 1ull);
+      atomicAdd(&p.ctr->done, 1ull);                                      // cases of the pass that are done (the lingering wavefronts watch it)
+      atomicAdd(&p.ctr->out_bytes, (unsigned long long)total);                  // the batch's totals on the device (eh_result_summary: one small copy instead of n lengths and n statuses)
+      atomicAdd(&p.ctr->by_status[c.status >= 0 && c.status < 6 ? c.status : 1], 1ull);
     }
     // larger areas the case borrowed go back to the pool (the output has been copied out of them)
     wave_sync();
@@ -374,21 +372,20 @@ __global__ void __launch_bounds__(64, EH_WAVES_PER_SIMD) eh_mutate_kernel(const 
   wave_sync();
   unsigned long long left = 0;
   if (l == 0) {
-    atomicAdd(p.ticket + 7, __builtin_amdgcn_s_memrealtime() - wg_t0);
-    atomicAdd(p.ticket + CTR_OCC, case_ticks);
-    atomicAdd(p.ticket + CTR_OCC + 1, linger_ticks);
+    atomicAdd(&p.ctr->wg_ticks, __builtin_amdgcn_s_memrealtime() - wg_t0);
+    atomicAdd(&p.ctr->case_ticks, case_ticks);
+    atomicAdd(&p.ctr->linger_ticks, linger_ticks);
   }
-  if (l == 0) left = atomicAdd(p.ticket + 6, 1ull);
+  if (l == 0) left = atomicAdd(&p.ctr->left, 1ull);
   if (uni64(left) + 1 == (unsigned long long)gridDim.x && p.summary_out) {
-    if (l < 6) sys_store(p.summary_out + 3 + l, co_ld64(p.ticket + CTR_STATUS + l));
-    if (l == 6) { sys_store(p.summary_out + 1, co_ld64(p.ticket + 5)); sys_store(p.summary_out + 2, p.n); }
-    if (l == 7) { sys_store(p.summary_out + 10, co_ld64(p.ticket + 7)); sys_store(p.summary_out + 11, co_ld64(p.ticket + CTR_OCC)); sys_store(p.summary_out + 12, co_ld64(p.ticket + CTR_OCC + 1)); sys_store(p.summary_out + 13, (unsigned long long)gridDim.x); }
+    if (l < 6) sys_store(&p.summary_out->by_status[l], co_ld64(&p.ctr->by_status[l]));
+    if (l == 6) { sys_store(&p.summary_out->out_bytes, co_ld64(&p.ctr->out_bytes)); sys_store(&p.summary_out->n, p.n); }
+    if (l == 7) { sys_store(&p.summary_out->wg_ticks, co_ld64(&p.ctr->wg_ticks)); sys_store(&p.summary_out->case_ticks, co_ld64(&p.ctr->case_ticks)); sys_store(&p.summary_out->linger_ticks, co_ld64(&p.ctr->linger_ticks)); sys_store(&p.summary_out->workgroups, (unsigned long long)gridDim.x); }
     wave_sync();
-    if (l == 0) sys_store(p.summary_out + 9, p.batch_seq);
+    if (l == 0) sys_store(&p.summary_out->seq, p.batch_seq);
   }
 }
 
-// kernel-level self tests of the byte movers (driven by tests/test_gpu_primitives.py)
 // =============================================================================================
 // EH_FLAG_ORDERED_OUTPUT: compaction of the completion-ordered arena into case order
 // =============================================================================================

@@ -359,14 +359,14 @@ __device__ __noinline__ bool fuse_lists(Ctx&, cbptr A, uint32_t la, cbptr B, uin
       cbptr B2 = A2;
       if (sym) lb2 = la2; else { B2 = fr_reduce(c, B, &lb2, R); if (!B2) return false; }
       if ((uint64_t)la2 + lb2 <= ((uint64_t)la + lb) / 4u * 3u) {
-        EH_PT(c, 97);                                              // eh_result_prof 97: finding + making the cuts, calls that took them; 98: calls that found none
+        EH_PT(c, PROF_FR_CUTS);                                              // eh_result_prof 97: finding + making the cuts, calls that took them; 98: calls that found none
         c.fp_on = 1;
         bool ok;
         if ((sym ? (uint64_t)la2 : (uint64_t)la2 + lb2) <= FL_NMAX && !(c.p->flags & EH_FLAG_FUSE_NO_LDS)) ok = fuse_jump_lds(c, A2, la2, B2, lb2, sym, &from, &tpos, &prof_rounds);
         else ok = fuse_jump_stream(c, A2, la2, B2, lb2, sym, &from, &tpos, &prof_rounds);
         c.fp_on = 0;
         if (!ok) return false;
-        EH_PT(c, 54);                                              // eh_result_prof 54: the search on the shortened lists; 55: the node's members found in the original lists
+        EH_PT(c, PROF_FR_SEARCH);                                              // eh_result_prof 54: the search on the shortened lists; 55: the node's members found in the original lists
         // any_position_pair/1 (:73-77) over the ORIGINAL lists: the members of the node are the occurrences of its g-gram
         const uint32_t g = c.fp_g, par = g & 1u;
         from = la; tpos = lb;
@@ -381,11 +381,11 @@ __device__ __noinline__ bool fuse_lists(Ctx&, cbptr A, uint32_t la, cbptr B, uin
           const uint32_t tc0 = sym ? fc0 : fr_occ(B, lb, limB, key, g, FR_NONE, nullptr), tc = tc0 + c.fp_bB;
           if (tc > 0) { uint32_t j = rng_rand(c.rng, tc); j = par ? tc - 1u - j : j; if (j < tc0) { (void)fr_occ(B, lb, limB, key, g, j, &pos); tpos = uni(pos) + g; } }
         }
-        EH_PT(c, 55);
+        EH_PT(c, PROF_FR_MEMBERS);
         goto jump;
       }
     }
-    EH_PT(c, 98);
+    EH_PT(c, PROF_FR_NO_CUT);
     c.ws_used = mark;                                              // (no cut worth it: the copies go)
   }
   if ((sym ? (uint64_t)la : (uint64_t)la + lb) <= FL_NMAX && !(c.p->flags & EH_FLAG_FUSE_NO_LDS)) {     // small lists: sorted suffix entries in LDS (eh_fuse_lds.h)
@@ -432,8 +432,8 @@ jump:
 #ifdef EH_PROF
   {                                                                // slots 112..125: fuse calls by log2(la + lb), 126: rounds
     uint32_t tot = la + lb, b = 0; while ((256u << b) < tot && b < 13) b++;
-    EH_PT(c, 112 + b);
-    if (EH_LANE == 0) { atomicAdd(&c.p->prof[2 * 126], (unsigned long long)prof_rounds); atomicAdd(&c.p->prof[2 * 126 + 1], 1ull); }
+    EH_PT(c, PROF_FUSE_BY_SIZE + b);
+    if (EH_LANE == 0) { atomicAdd(&c.p->prof[2 * PROF_FUSE_ROUNDS], (unsigned long long)prof_rounds); atomicAdd(&c.p->prof[2 * PROF_FUSE_ROUNDS + 1], 1ull); }
   }
 #endif
   c.ws_used = mark;                                                // release all tables
@@ -447,8 +447,6 @@ jump:
   *out = dst; *outlen = nl;
   return true;
 }
-
-struct FoState { uint64_t ptr; uint32_t len; uint32_t has; };
 
 __device__ __noinline__ int muta_fuse(Ctx&, int fn, EH_G FoState* fo) {
   EH_CTX;

@@ -482,9 +482,9 @@ __device__ __noinline__ bool fuse_jump_stream(Ctx&, cbptr A, uint32_t la, cbptr 
       wave_sync();
     }
     const uint32_t nwords = nn * 8u;
-    EH_PT(c, 100);
+    EH_PT(c, PROF_FB_ALLOC);
     if (!have_bits) for (int s = 0; s < nside; s++) fb_bits0(S[s], len[s], M[s]);     // only generation 0 comes here
-    EH_PT(c, 101);
+    EH_PT(c, PROF_FB_BITS0);
     // ---- the member at len-1 of this round: alone in its group?
     uint32_t e_pos[2] = {FB_DEAD, FB_DEAD}, e_alone[2] = {0, 0}, e_w[2] = {0, 0}, e_bit[2] = {0, 0};
     for (int s = 0; s < nside; s++) {
@@ -497,13 +497,13 @@ __device__ __noinline__ bool fuse_jump_stream(Ctx&, cbptr A, uint32_t la, cbptr 
       e_alone[s] = fb_end_member(M[s], cur_n1 ? N1[s] : nullptr, id, b) ? 0u : 1u;
     }
     wave_sync();
-    EH_PT(c, 102);
+    EH_PT(c, PROF_FB_ETEST);
     // ---- children
     const bool forced = !sym && e_pos[0] != FB_DEAD && e_alone[0];
     uint32_t sp = FB_DEAD, nfull = 0;
     uint32_t nchild = fb_scan(M[0], sym ? nullptr : M[1], cur_n1 ? N1[0] : nullptr, (cur_n1 && !sym) ? N1[1] : nullptr, nwords,
                               forced ? e_w[0] : FB_DEAD, forced ? e_bit[0] : 0u, RK, SC, &sp, &nfull);
-    EH_PT(c, 103);
+    EH_PT(c, PROF_FB_SCAN);
     if (nchild == 0) break;                                        // NoDesp =:= [] -> any_position_pair(Nodes)
     // ---- commit: ids of generation g+1 (+ the next-byte tables of the next round when it is going to run)
     fuel -= (int64_t)nchild;
@@ -529,7 +529,7 @@ __device__ __noinline__ bool fuse_jump_stream(Ctx&, cbptr A, uint32_t la, cbptr 
     for (int s = 0; s < nside; s++) {
       if (lds) { for (uint32_t i = l; i < nchild * 8u; i += 64) g_fuse_lds[FB_LDS_NEXT + i] = 0; lanes_sync(); }
       if (n1_lds) { for (uint32_t i = l; i < nchild; i += 64) g_fuse_lds[FB_LDS_NEXT + i] = 0; lanes_sync(); }
-      EH_PT(c, 104);
+      EH_PT(c, PROF_FB_CLEAR);
       // the member at len-1: leaves when it was inserted first (alone, or an odd generation).  One list on both sides:
       // alone = the special node = the member itself, now empty, so it stays.
       bool ek = sym ? (!e_alone[0] && (g & 1u)) : (e_alone[s] || (g & 1u));
@@ -553,7 +553,7 @@ __device__ __noinline__ bool fuse_jump_stream(Ctx&, cbptr A, uint32_t la, cbptr 
               : ins == 2 ? fb_pass<2>(S[s], len[s], ids[s], g, RK, look, sc_lds, kill, ek ? e_pos[s] : FB_DEAD, len[s], mn, nullptr)
               : fb_pass<0>(S[s], len[s], ids[s], g, RK, look, sc_lds, kill, ek ? e_pos[s] : FB_DEAD, len[s], mn, nullptr);
       entries += alive;
-      EH_PT(c, lds ? 105 : (n1_lds ? 96 : (n1 ? 111 : (next ? (nchild * 8u <= FB_TEST_WORDS ? 110 : 106) : 107))));
+      EH_PT(c, lds ? PROF_FB_PASS_LDS : (n1_lds ? PROF_FB_PASS_N1_LDS : (n1 ? PROF_FB_PASS_N1 : (next ? (nchild * 8u <= FB_TEST_WORDS ? PROF_FB_PASS_TEST : PROF_FB_PASS_GLOBAL) : PROF_FB_PASS_LAST))));
       if (lds) { lanes_sync(); for (uint32_t i = l; i < nchild * 8u; i += 64) M[s][i] = g_fuse_lds[FB_LDS_NEXT + i]; wave_sync(); }
       if (n1_lds) { lanes_sync(); for (uint32_t i = l; i < nchild; i += 64) N1[s][i] = g_fuse_lds[FB_LDS_NEXT + i]; wave_sync(); }
     }
@@ -561,7 +561,7 @@ __device__ __noinline__ bool fuse_jump_stream(Ctx&, cbptr A, uint32_t la, cbptr 
     gen_entries = entries;
     special_node = forced ? sp : FB_DEAD;
     nn = nchild; g++; have_bits = next; cur_n1 = n1;
-    EH_PT(c, 108);
+    EH_PT(c, PROF_FB_TAIL);
     (*rounds)++;
   }
   // any_position_pair/1 (:73-77); odd generations are stored reversed
@@ -579,7 +579,7 @@ __device__ __noinline__ bool fuse_jump_stream(Ctx&, cbptr A, uint32_t la, cbptr 
     c.fp_bA = (ml + g == la) ? 1u : 0u;
     if (sym) c.fp_bB = c.fp_bA;
     else { const uint32_t tcn = fb_count(ids[1], lb, node); c.fp_bB = (tcn > 0 && fb_find(ids[1], lb, node, tcn - 1u) + g == lb) ? 1u : 0u; }
-    EH_PT(c, 109);
+    EH_PT(c, PROF_FB_SELECT);
     return true;
   }
   if (g == 0) {                                                    // the one node of all suffixes
@@ -594,7 +594,7 @@ __device__ __noinline__ bool fuse_jump_stream(Ctx&, cbptr A, uint32_t la, cbptr 
   if (fc > 0) { uint32_t j = rng_rand(c.rng, fc); f = fb_find(ids[0], la, node, par ? fc - 1 - j : j) + g; }
   if (tc > 0) { uint32_t j = rng_rand(c.rng, tc); t = fb_find(sym ? ids[0] : ids[1], lb, node, par ? tc - 1 - j : j) + g; }
   *from = f; *tpos = t;
-  EH_PT(c, 109);
+  EH_PT(c, PROF_FB_SELECT);
   return true;
 }
 

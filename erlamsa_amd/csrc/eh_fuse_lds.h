@@ -445,7 +445,7 @@ __device__ __noinline__ bool fuse_jump_lds(Ctx&, cbptr A, uint32_t la, cbptr B, 
       if (c.work > c.work_budget) { c.status = CASE_BUDGET; return false; }
     }
 #ifdef EH_PROF
-    const int pslot = (st.sym && st.multi == 0) ? 102 : (st.g == 0 ? 100 : 101);   // eh_result_prof: first round / later rounds / rounds of single members
+    const int pslot = (st.sym && st.multi == 0) ? PROF_FL_SINGLE : (st.g == 0 ? PROF_FL_ROUND1 : PROF_FL_ROUNDS);   // eh_result_prof: first round / later rounds / rounds of single members
 #endif
     uint32_t nchild = fl_round(st);
     EH_PT(c, pslot);
@@ -485,7 +485,7 @@ __device__ __noinline__ bool fuse_jump_lds(Ctx&, cbptr A, uint32_t la, cbptr B, 
     c.fp_special = (fc == 1u && e0 + st.g == la) ? 1u : 0u;
     c.fp_bA = (el + st.g == la) ? 1u : 0u;
     c.fp_bB = sym ? c.fp_bA : ((tc > 0 && uni((uint32_t)E[b - 1u]) - la + st.g == lb) ? 1u : 0u);
-    EH_PT(c, 103);
+    EH_PT(c, PROF_FL_SELECT);
     return true;
   }
   bool special_t = false;
@@ -497,7 +497,7 @@ __device__ __noinline__ bool fuse_jump_lds(Ctx&, cbptr A, uint32_t la, cbptr B, 
     if (!special_t) { uint32_t idx = sym ? a + (par ? tc - 1u - j : j) : a + fc + (par ? tc - 1u - j : j); uint32_t e = (uint32_t)E[idx]; *tpos = (sym ? e : e - la) + st.g; }
   }
   *from = uni(*from); *tpos = uni(*tpos);
-  EH_PT(c, 103);
+  EH_PT(c, PROF_FL_SELECT);
   return true;
 }
 

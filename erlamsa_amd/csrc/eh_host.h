@@ -50,7 +50,7 @@ struct DevPool {
   int refs = 0;
   int ntiers = 0;                                       // tiers 1..ntiers
   DevBuf<uint8_t> base[POOL_TIERS + 1]; uint64_t stride[POOL_TIERS + 1] = {}, cap[POOL_TIERS + 1] = {}; uint32_t cnt[POOL_TIERS + 1] = {};
-  DevBuf<uint32_t> d_rings; uint32_t* ring[POOL_TIERS + 1] = {}; DevBuf<unsigned long long> d_ctr;
+  DevBuf<uint32_t> d_rings; uint32_t* ring[POOL_TIERS + 1] = {}; DevBuf<PoolCounters> d_ctr;
   DevBuf<CoBoard> d_board;                              // cooperative execution: the board every context of the device posts on (eh_common.h)
 };
 
@@ -79,11 +79,11 @@ struct Results {
   DevBuf<uint64_t> d_off, d_len, d_draws, d_cycles, d_peak, d_toff;
   DevBuf<int32_t> d_status, d_lastm;
   DevBuf<uint32_t> d_tlen;
-  DevBuf<unsigned long long> d_counters;  // [0] ticket, [1] out cursor, [2] input bytes, [3] cases done, [4] lingering wavefronts, [5] output bytes, [6] workgroups that left, [8, 264) EH_PROF, [264, 270) cases by status
+  DevBuf<BatchCounters> d_counters;                     // one: the batch's counters (eh_common.h)
   DevBuf<KParams> d_params;                             // argument block of eh_mutate_kernel
   DevBuf<RunState> d_run;
   DevBuf<uint8_t> d_seeds;                              // mode 1, SEED_ROW bytes per case: three int64 seeds for every case, then a uint32 profile id for every case
-  unsigned long long* h_sum = nullptr; uint64_t batch_seq = 0;   // page-locked: the last batch's totals, written by the kernel (KParams::summary_out)
+  BatchSummary* h_sum = nullptr; uint64_t batch_seq = 0;   // page-locked: the last batch's totals, written by the kernel (KParams::summary_out)
   hipEvent_t ev0 = nullptr, ev1 = nullptr;              // around eh_mutate_kernel (eh_create)
   hipStream_t last_stream = nullptr;
   hipStream_t own_stream = nullptr;                     // eh_stream: a stream of the context's own (non-blocking), made on first request

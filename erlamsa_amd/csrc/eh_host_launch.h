@@ -59,10 +59,10 @@ static int launch(eh_ctx* ctx, int mode, const int64_t seed[3], uint64_t first_c
   if (!ctx->corpus.h_off.empty()) in_bytes = ctx->corpus.h_off[corpus_first + n] - ctx->corpus.h_off[corpus_first];
   int rc = reserve(ctx, n, in_bytes);
   if (rc) return rc;
-  HIPCHK(ctx, ctx->res.d_counters.grow(512));
+  HIPCHK(ctx, ctx->res.d_counters.grow(1));
   HIPCHK(ctx, ctx->res.d_run.grow(1));
   HIPCHK(ctx, ctx->res.d_params.grow(1));
-  if (!ctx->res.h_sum) { HIPCHK(ctx, hipHostMalloc((void**)&ctx->res.h_sum, 128, hipHostMallocDefault)); memset(ctx->res.h_sum, 0, 128); }
+  if (!ctx->res.h_sum) { HIPCHK(ctx, hipHostMalloc((void**)&ctx->res.h_sum, sizeof(BatchSummary), hipHostMallocDefault)); memset(ctx->res.h_sum, 0, sizeof(BatchSummary)); }
 
   KParams p;
   memset(&p, 0, sizeof(p));
@@ -73,15 +73,15 @@ static int launch(eh_ctx* ctx, int mode, const int64_t seed[3], uint64_t first_c
   p.work_cap = pl->work_cap;
   p.work_budget = ctx->work_budget;                                            // 0 = no budget (the default)
   p.fuse_stream_min = ctx->fuse_stream_min;
-  p.out = dp(ctx->res.d_out); p.out_cap = ctx->res.d_out.cap; p.out_cursor = dp(ctx->res.d_counters + 1);
+  p.out = dp(ctx->res.d_out); p.out_cap = ctx->res.d_out.cap; p.out_cursor = dp(&ctx->res.d_counters.p->out_cursor);
   p.out_off = dp(ctx->res.d_off); p.out_len = dp(ctx->res.d_len); p.status = dp(ctx->res.d_status); p.draws = dp(ctx->res.d_draws); p.lastm = dp(ctx->res.d_lastm); p.cycles = dp(ctx->res.d_cycles); p.peak = dp(ctx->res.d_peak); p.trace_off = dp(ctx->res.d_toff); p.trace_len = dp(ctx->res.d_tlen); p.flags = ctx->flags;
-  p.ticket = dp(ctx->res.d_counters); p.in_bytes = dp(ctx->res.d_counters + 2); p.prof = dp(ctx->res.d_counters + 8);   // counters [8, 264) = prof
+  p.ctr = dp(ctx->res.d_counters); p.in_bytes = dp(&ctx->res.d_counters.p->in_bytes); p.prof = dp(ctx->res.d_counters.p->prof);
   p.slot_base = dp(ctx->d_slots); p.slot_stride = ctx->slot_stride;
   p.ntiers = pl->ntiers; p.pool_ctr = dp(pl->d_ctr); p.pool_cap[0] = pl->work_cap;
   p.board = (ctx->flags & EH_FLAG_NO_COOP) ? dp((CoBoard*)nullptr) : dp(pl->d_board);
   co_defaults(&p, ctx->cus);
   p.summary_out = dp(ctx->res.h_sum); p.batch_seq = ++ctx->res.batch_seq;
-  if (n == 0) { memset(ctx->res.h_sum, 0, 128); ctx->res.h_sum[9] = ctx->res.batch_seq; }      // (no mutate kernel: nothing else would write it)
+  if (n == 0) { memset(ctx->res.h_sum, 0, sizeof(BatchSummary)); ctx->res.h_sum->seq = ctx->res.batch_seq; }      // (no mutate kernel: nothing else would write it)
   for (int t = 1; t <= pl->ntiers; t++) { p.pool_base[t] = dp(pl->base[t]); p.pool_stride[t] = pl->stride[t]; p.pool_cap[t] = pl->cap[t]; p.pool_cnt[t] = pl->cnt[t]; p.pool_ring[t] = dp(pl->ring[t]); }
   // persistent workgroups, each pulling cases from the ticket counter.  Batches in flight on several streams may
   // oversubscribe the device: the dispatcher starts a batch's workgroups as those of earlier ones leave.
@@ -89,7 +89,7 @@ static int launch(eh_ctx* ctx, int mode, const int64_t seed[3], uint64_t first_c
 
   // counters, argument block and run state by ONE one-wavefront kernel (no fill / copy kernels of the runtime: see eh_prologue_kernel)
   hipLaunchKernelGGL(eh_prologue_kernel, dim3(1), dim3(64), 0, st, p, mode == 0 ? seed[0] : 0, mode == 0 ? seed[1] : 0, mode == 0 ? seed[2] : 0,
-                     ctx->res.d_run, ctx->res.d_params, ctx->res.d_counters);
+                     ctx->res.d_run, ctx->res.d_params, (unsigned long long*)ctx->res.d_counters.p);
   HIPCHK(ctx, hipEventRecord(ctx->res.ev0, st));
   if (n > 0) hipLaunchKernelGGL(eh_mutate_kernel, dim3(grid0), dim3(64), 0, st, (const KParams*)ctx->res.d_params);
   HIPCHK(ctx, hipEventRecord(ctx->res.ev1, st));

@@ -65,17 +65,17 @@ static int pool_acquire(eh_ctx* ctx, uint64_t work_cap, uint64_t big, uint64_t p
   uint64_t nring = 4;
   for (int t = 1; t <= pl->ntiers; t++) nring += pl->cnt[t];
   std::vector<uint32_t> init(nring);
-  std::vector<unsigned long long> ctr(64, 0ull);
-  if (pl->d_rings.grow(nring) != hipSuccess || pl->d_ctr.grow(64) != hipSuccess) { pool_free(pl); ctx->err = "work-area pool: out of device memory"; return EH_E_NOMEM; }
+  PoolCounters ctr; memset(&ctr, 0, sizeof ctr);
+  if (pl->d_rings.grow(nring) != hipSuccess || pl->d_ctr.grow(1) != hipSuccess) { pool_free(pl); ctx->err = "work-area pool: out of device memory"; return EH_E_NOMEM; }
   uint64_t o = 0;
   for (int t = 1; t <= pl->ntiers; t++) {
     pl->ring[t] = pl->d_rings + o;
     for (uint32_t k = 0; k < pl->cnt[t]; k++) init[o + k] = k;
-    ctr[2 * t] = 0; ctr[2 * t + 1] = pl->cnt[t];                                   // pop tickets, push tickets
+    ctr.ring[t].pop = 0; ctr.ring[t].push = pl->cnt[t];
     o += pl->cnt[t];
   }
   if (hipMemcpy(pl->d_rings, init.data(), nring * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(pl->d_ctr, ctr.data(), 64 * 8, hipMemcpyHostToDevice) != hipSuccess) { pool_free(pl); ctx->err = "work-area pool: hipMemcpy failed"; return EH_E_HIP; }
+      hipMemcpy(pl->d_ctr, &ctr, sizeof ctr, hipMemcpyHostToDevice) != hipSuccess) { pool_free(pl); ctx->err = "work-area pool: hipMemcpy failed"; return EH_E_HIP; }
   if (pl->d_board.grow(1) != hipSuccess || hipMemset(pl->d_board, 0, sizeof(CoBoard)) != hipSuccess) { pool_free(pl); ctx->err = "work-area pool: no memory for the cooperation board"; return EH_E_NOMEM; }
   pl->refs = 1; g_pools.push_back(pl); ctx->pool = pl;
   return EH_OK;
@@ -100,12 +100,12 @@ int eh_pool_stats(eh_ctx* ctx, uint64_t* out /* 64 values */) {
   if (!ctx || !out) return EH_E_INVALID;
   if (!ctx->pool) { ctx->err = "no work-area pool yet (eh_reserve or a first batch creates it)"; return EH_E_STATE; }
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  uint64_t raw[64];
-  HIPCHK(ctx, hipMemcpy(raw, ctx->pool->d_ctr, 64 * 8, hipMemcpyDeviceToHost));   // (a plain copy: fine while batches run)
-  memcpy(out, raw, 40 * 8);
+  PoolCounters raw;
+  HIPCHK(ctx, hipMemcpy(&raw, ctx->pool->d_ctr, sizeof raw, hipMemcpyDeviceToHost));   // (a plain copy: fine while batches run)
+  memcpy(out, &raw, offsetof(PoolCounters, most_out));                                  // words [0, 40): rings, wait ticks, waits
   out[40] = (uint64_t)ctx->pool->ntiers;
   for (int t = 0; t <= POOL_TIERS; t++) {
-    out[41 + t] = t >= 1 && t <= ctx->pool->ntiers ? (uint64_t)ctx->pool->cnt[t] | (raw[40 + t] << 32) : 0;   // areas | the most that were out at once
+    out[41 + t] = t >= 1 && t <= ctx->pool->ntiers ? (uint64_t)ctx->pool->cnt[t] | (raw.most_out[t] << 32) : 0;   // areas | the most that were out at once
     out[51 + t] = t <= ctx->pool->ntiers ? ctx->pool->cap[t] : 0;
   }
   out[61] = (uint64_t)ctx->pool->refs; out[62] = ctx->nslots; out[63] = 0;
@@ -117,6 +117,6 @@ int eh_coop_stats(eh_ctx* ctx, uint64_t* out /* 8 values */) {
   if (!ctx || !out) return EH_E_INVALID;
   if (!ctx->pool) { ctx->err = "no work-area pool yet (eh_reserve or a first batch creates it)"; return EH_E_STATE; }
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  HIPCHK(ctx, hipMemcpy(out, (const uint8_t*)ctx->pool->d_board.p + offsetof(CoBoard, stat), 8 * 8, hipMemcpyDeviceToHost));
+  HIPCHK(ctx, hipMemcpy(out, (const uint8_t*)ctx->pool->d_board.p + offsetof(CoBoard, stat), sizeof(CoBoard::stat), hipMemcpyDeviceToHost));
   return EH_OK;
 }

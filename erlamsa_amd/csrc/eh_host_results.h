@@ -24,7 +24,7 @@ int eh_result_device(eh_ctx* ctx, const uint8_t** d_data, const uint64_t** d_off
   if (total) {
     unsigned long long cur = 0;
     if (ctx->res.ordered) HIPCHK(ctx, hipMemcpy(&cur, ctx->res.d_ord + ctx->res.last_n, 8, hipMemcpyDeviceToHost));   // bytes of the compact, case-ordered buffer
-    else HIPCHK(ctx, hipMemcpy(&cur, ctx->res.d_counters + 1, 8, hipMemcpyDeviceToHost));                     // bump cursor of the completion-ordered arena (16-byte granules)
+    else HIPCHK(ctx, hipMemcpy(&cur, &ctx->res.d_counters.p->out_cursor, 8, hipMemcpyDeviceToHost));         // bump cursor of the completion-ordered arena (16-byte granules)
     *total = cur > ctx->res.d_out.cap ? ctx->res.d_out.cap : cur;               // the cursor runs past the arena after EH_CASE_ARENA_FULL
   }
   return EH_OK;
@@ -45,28 +45,29 @@ static int result_totals(eh_ctx* ctx, uint64_t* in_bytes, uint64_t* out_bytes, u
 int eh_result_totals(eh_ctx* ctx, uint64_t* in_bytes, uint64_t* out_bytes, uint64_t* n_cases) { return ctx ? result_totals(ctx, in_bytes, out_bytes, n_cases) : EH_E_INVALID; }
 // The last batch's totals in h_sum, for `who`: the kernel's last workgroup wrote them into page-locked memory, stamped with the
 // batch's number, so no copy call is needed - and no runtime call at all for a batch that eh_batch_done has seen end.
-static int totals_arrived(eh_ctx* ctx, const char* who, volatile unsigned long long** hs) {
+static int totals_arrived(eh_ctx* ctx, const char* who, const volatile BatchSummary** hs) {
   if (int rc = result_ready(ctx, false)) return rc;
   if (hipEventQuery(ctx->res.ev1) != hipSuccess) { (void)hipGetLastError(); int rc = eh_sync(ctx); if (rc) return rc; }
   *hs = ctx->res.h_sum;
-  if (!*hs || (*hs)[9] != ctx->res.batch_seq) { ctx->err = std::string(who) + ": the batch's totals have not arrived in host memory"; return EH_E_HIP; }
+  if (!*hs || (*hs)->seq != ctx->res.batch_seq) { ctx->err = std::string(who) + ": the batch's totals have not arrived in host memory"; return EH_E_HIP; }
   return EH_OK;
 }
 // out[0] input bytes, out[1] output bytes, out[2] cases, out[3 + s] cases that ended with status s (0..5) - summed by the kernel,
 // one copy of 2 KiB: what a host loop over many small batches reads per batch instead of n lengths and n statuses.
 int eh_result_summary(eh_ctx* ctx, uint64_t* out /* 9 values */) {
   if (!ctx || !out) return EH_E_INVALID;
-  volatile unsigned long long* hs = nullptr;
+  const volatile BatchSummary* hs = nullptr;
   if (int rc = totals_arrived(ctx, "eh_result_summary", &hs)) return rc;
-  out[0] = ctx->res.last_in_bytes; out[1] = hs[1]; out[2] = ctx->res.last_n;
-  for (int k = 0; k < 6; k++) out[3 + k] = hs[3 + k];
+  out[0] = ctx->res.last_in_bytes; out[1] = hs->out_bytes; out[2] = ctx->res.last_n;
+  for (int k = 0; k < 6; k++) out[3 + k] = hs->by_status[k];
   return EH_OK;
 }
 int eh_result_occupancy(eh_ctx* ctx, uint64_t* out /* 5 values */) {
   if (!ctx || !out) return EH_E_INVALID;
-  volatile unsigned long long* hs = nullptr;
+  const volatile BatchSummary* hs = nullptr;
   if (int rc = totals_arrived(ctx, "eh_result_occupancy", &hs)) return rc;
-  for (int k = 0; k < 4; k++) out[k] = ctx->res.last_n ? hs[10 + k] : 0;
+  const bool ran = ctx->res.last_n != 0;                                      // (a batch of no cases ran no mutate kernel)
+  out[0] = ran ? hs->wg_ticks : 0; out[1] = ran ? hs->case_ticks : 0; out[2] = ran ? hs->linger_ticks : 0; out[3] = ran ? hs->workgroups : 0;
   out[4] = (uint64_t)ctx->cus * 4u * EH_WAVES_PER_SIMD;
   return EH_OK;
 }
@@ -253,6 +254,6 @@ int eh_result_peak(eh_ctx* ctx, uint64_t* peak) {
 int eh_result_prof(eh_ctx* ctx, uint64_t* prof /* 256 values */) {
   if (!ctx || !prof) return EH_E_INVALID;
   int rc = result_ready(ctx); if (rc) return rc;
-  HIPCHK(ctx, hipMemcpy(prof, ctx->res.d_counters + 8, 256 * 8, hipMemcpyDeviceToHost));
+  HIPCHK(ctx, hipMemcpy(prof, ctx->res.d_counters.p->prof, sizeof(BatchCounters::prof), hipMemcpyDeviceToHost));
   return EH_OK;
 }

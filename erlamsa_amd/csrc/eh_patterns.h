@@ -41,15 +41,6 @@ __device__ __noinline__ void gen_force(Ctx&);   // the file / jump generators' f
 enum Act { A_RUN_PAT, A_MUTATE_ONCE, A_LOOP, A_CONT, A_TERMINAL, A_DONE };
 enum ContKind { C_EMIT, C_ND, C_BU, C_PAT };
 
-struct PatFrame {           // a sizer/csum wrapper waiting for its inner evaluation (prepare4sizer)
-  int kind;                 // P_SZ or P_CS
-  int em_field;             // sz: index of the length-field piece in the emit list; cs: first inner piece
-  bptr field;           // sz: the Size/8 bytes to fill in
-  uint32_t size_bits, big;  // sz
-  uint64_t tail_ptr; uint32_t tail_len;   // sz: TailBin
-  uint32_t crc;             // cs: 1 crc32, 0 xor8
-};
-
 // get_possible_csum_locations/1 + rand_elem (erlamsa_field_predict.erl:131-161).
 // Returns 1 with (*crc,*plen,*blen), 0 for no candidate, -1 on failure.
 __device__ __noinline__ int pick_csum(Ctx&, cbptr H, uint32_t L, uint32_t* crc, uint32_t* plen, uint32_t* blen) {
@@ -158,20 +149,20 @@ __device__ __noinline__ int pick_csum(Ctx&, cbptr H, uint32_t L, uint32_t* crc, 
 // the one that evaluation returns: the scheduler's list (LaneTab), the lis / lrs / fo states and, when the result is thrown
 // away, the meta trace are put back.  What is parked lives in the work area until the frame is popped.
 // ---------------------------------------------------------------------------------------------------------------------
-struct MutatorSave { uint32_t lt_pri[64], lt_meta[64]; uint32_t aux_save[180]; int32_t nfs; uint32_t ntrace; };   // aux + 0 .. 720: StState x 2 + FoState
+struct MutatorSave { uint32_t lt_pri[64], lt_meta[64]; uint32_t aux_save[sizeof(NestState) / 4]; int32_t nfs; uint32_t ntrace; };   // aux_save: SlotAux::nest
 EH_DEV void mutator_save(Ctx& c, EH_G MutatorSave* m, uint32_t e_pri, uint32_t e_meta) {
   const int l = EH_LANE;
   m->lt_pri[l] = e_pri; m->lt_meta[l] = e_meta;
-  cwptr ax = (cwptr)c.aux;
-  for (int i = l; i < 180; i += 64) m->aux_save[i] = ax[i];
+  cwptr ax = (cwptr)&c.aux->nest;
+  for (int i = l; i < (int)(sizeof(NestState) / 4); i += 64) m->aux_save[i] = ax[i];
   if (l == 0) { m->nfs = c.nfs; m->ntrace = c.ntrace; }
   wave_sync();
 }
 EH_DEV uint64_t mutator_restore(Ctx& c, const EH_G MutatorSave* m, bool trace_too) {   // returns the lane's (e_pri, e_meta)
   const int l = EH_LANE;
   wave_sync();
-  wptr ax = (wptr)c.aux;
-  for (int i = l; i < 180; i += 64) ax[i] = m->aux_save[i];
+  wptr ax = (wptr)&c.aux->nest;
+  for (int i = l; i < (int)(sizeof(NestState) / 4); i += 64) ax[i] = m->aux_save[i];
   c.nfs = (int)uni((uint32_t)m->nfs);
   if (trace_too) c.ntrace = uni(m->ntrace);
   wave_sync();
@@ -430,7 +421,7 @@ __device__ __noinline__ uint64_t pat_container_end(Ctx&, uint32_t e_pri, uint32_
 EH_DEV void run_patterns(Ctx& c, LaneTab& lt, int pat) {
   int act = A_RUN_PAT, cont = C_EMIT, contpat = 0; uint32_t ip = 0;
   int guard = 0;
-  EH_G PatFrame* frames = (EH_G PatFrame*)(c.aux + 1152); int nfr = 0;     // wrapper stack lives in slot memory
+  EH_G PatFrame* frames = c.aux->frames; int nfr = 0;     // wrapper stack lives in slot memory
   while (act != A_DONE && c.status == CASE_OK) {
     if (++guard > 1000000) { EH_SET_OVERFLOW(c, 305); break; }
     switch (act) {
@@ -472,7 +463,7 @@ EH_DEV void run_patterns(Ctx& c, LaneTab& lt, int pat) {
                   if (c.status != CASE_OVERFLOW || c.ovf_need == 0 || !ws_regrow(c, mark, &last_tier)) break;
                   c.rng = rng0;
                 }
-                EH_PT(c, 60);
+                EH_PT(c, PROF_PAT_PICK_LEN);
               }
               if (r < 0) break;
               if (r == 0) tr_aa(c, AT_sizer, AT_failed);                              // [{sizer, failed} | Meta] :85
@@ -498,7 +489,7 @@ EH_DEV void run_patterns(Ctx& c, LaneTab& lt, int pat) {
               uint32_t iscrc, plen, blen;
               EH_PT0;
               int r = pick_csum(c, H, b.len, &iscrc, &plen, &blen);
-              EH_PT(c, 59);
+              EH_PT(c, PROF_PAT_PICK_CSUM);
               if (r < 0) break;
               if (r == 0) tr_aa(c, AT_csum, AT_failed);                               // :119
               if (r == 1) {
@@ -516,7 +507,7 @@ EH_DEV void run_patterns(Ctx& c, LaneTab& lt, int pat) {
             } else if (pat == P_AR || pat == P_CP) {                                  // mutate_once_archiver :165-214, mutate_once_compressed :216-260
               EH_PT0;
               uint64_t e = pat_container_begin(c, lt.e_pri, lt.e_meta, pat, frames, nfr, ip, contpat);
-              EH_PT(c, pat == P_CP ? 63 : 78);
+              EH_PT(c, pat == P_CP ? PROF_PAT_CP_BEGIN : PROF_PAT_AR_BEGIN);
               lt.e_pri = (uint32_t)(e >> 32); lt.e_meta = (uint32_t)e;
               if (c.pat_ret < 0) break;
               if (c.pat_ret == 2) { nfr++; act = A_LOOP; break; }                     // the rest of the chain on a payload: mutate_once_loop(Mutator, [], NextPat, Ip, Data, [])
@@ -571,7 +562,7 @@ EH_DEV void run_patterns(Ctx& c, LaneTab& lt, int pat) {
         if (f.kind == P_AR || f.kind == P_CP) {
           EH_PT0;
           uint64_t e = pat_container_end(c, lt.e_pri, lt.e_meta, f.kind, f.em_field, f.field, frames, nfr);
-          EH_PT(c, f.kind == P_CP ? 69 : 79);
+          EH_PT(c, f.kind == P_CP ? PROF_PAT_CP_END : PROF_PAT_AR_END);
           lt.e_pri = (uint32_t)(e >> 32); lt.e_meta = (uint32_t)e;
           if (c.pat_ret < 0) break;
           ip = c.pat_ip; cont = C_PAT; contpat = c.pat_cont;
@@ -595,9 +586,9 @@ EH_DEV void run_patterns(Ctx& c, LaneTab& lt, int pat) {
           uint64_t o = 0;
           for (int k = f.em_field; k < c.nem; k++) { Blk x = blk_load(c.em, k); wave_copy(blob + o, (cbptr)x.ptr, x.len); o += x.len; }
           wave_sync();
-          EH_PT(c, 61);
+          EH_PT(c, PROF_PAT_CS_BLOB);
           uint32_t cs = f.crc ? wave_crc32(blob, (uint32_t)tot) : wave_xor8(blob, (uint32_t)tot);
-          EH_PT(c, 62);
+          EH_PT(c, PROF_PAT_CS_SUM);
           uint32_t cb = f.crc ? 4u : 1u;
           if (EH_LANE == 0) put_field(blob + tot, cs, cb * 8, true);
           wave_sync();

@@ -361,7 +361,7 @@ __device__ __noinline__ int sgml_tokenize(Ctx&, cbptr H, uint32_t L, SgDoc* out)
 #define SG_SUB0() do { sub_t0 = __builtin_readcyclecounter(); } while (0)
 #define SG_SUB(k) do { uint64_t n_ = __builtin_readcyclecounter(); if (l == 0) { atomicAdd(&c.p->prof[2 * (k)], (unsigned long long)(n_ - sub_t0)); atomicAdd(&c.p->prof[2 * (k) + 1], 1ull); } sub_t0 = n_; } while (0)
 #define SG_CNT(k, v) do { if (l == 0) { atomicAdd(&c.p->prof[2 * (k)], (unsigned long long)(v)); atomicAdd(&c.p->prof[2 * (k) + 1], 1ull); } } while (0)
-  if (l == 0) { atomicAdd(&c.p->prof[2 * 117], (unsigned long long)(sub_t0 - ph1_t0)); atomicAdd(&c.p->prof[2 * 117 + 1], 1ull); atomicAdd(&c.p->prof[2 * 119], (unsigned long long)nev); atomicAdd(&c.p->prof[2 * 119 + 1], (unsigned long long)L); }
+  if (l == 0) { atomicAdd(&c.p->prof[2 * PROF_SG_PHASE1], (unsigned long long)(sub_t0 - ph1_t0)); atomicAdd(&c.p->prof[2 * PROF_SG_PHASE1 + 1], 1ull); atomicAdd(&c.p->prof[2 * PROF_SG_EVENTS], (unsigned long long)nev); atomicAdd(&c.p->prof[2 * PROF_SG_EVENTS + 1], (unsigned long long)L); }
   uint64_t tz_t0 = __builtin_readcyclecounter();
 #define SG_TZ(k) do { uint64_t n_ = __builtin_readcyclecounter(); if (l == 0) { atomicAdd(&c.p->prof[2 * (k)], (unsigned long long)(n_ - tz_t0)); atomicAdd(&c.p->prof[2 * (k) + 1], 1ull); } tz_t0 = n_; } while (0)
 #else
@@ -449,7 +449,7 @@ __device__ __noinline__ int sgml_tokenize(Ctx&, cbptr H, uint32_t L, SgDoc* out)
     }
     wave_sync();
 #ifdef EH_PROF
-    if (l == 0) { atomicAdd(&c.p->prof[2 * 116], (unsigned long long)(__builtin_readcyclecounter() - bn_t0)); atomicAdd(&c.p->prof[2 * 116 + 1], 1ull); }
+    if (l == 0) { atomicAdd(&c.p->prof[2 * PROF_SG_NEXT_STOP], (unsigned long long)(__builtin_readcyclecounter() - bn_t0)); atomicAdd(&c.p->prof[2 * PROF_SG_NEXT_STOP + 1], 1ull); }
 #endif
     return true;
   };
@@ -510,7 +510,7 @@ __device__ __noinline__ int sgml_tokenize(Ctx&, cbptr H, uint32_t L, SgDoc* out)
     uint32_t u = 0, D = 0, P = 0;
     const bool found = fr_find_cut(H + a, b - a, 0, &u, &D, &P) && P > 0;
 #ifdef EH_PROF
-    if (l == 0) { atomicAdd(&c.p->prof[2 * 95 + 1], 1ull); atomicAdd(&c.p->prof[2 * 95], found ? 1ull : 0ull); }      // searches, stretches found
+    if (l == 0) { atomicAdd(&c.p->prof[2 * PROF_SG_STRETCH + 1], 1ull); atomicAdd(&c.p->prof[2 * PROF_SG_STRETCH], found ? 1ull : 0ull); }      // searches, stretches found
 #endif
     if (!found) return false;
     rq_lo[rq_n] = a + u - P; rq_end[rq_n] = a + u + D; rq_P[rq_n] = P; rq_n++;
@@ -603,7 +603,7 @@ __device__ __noinline__ int sgml_tokenize(Ctx&, cbptr H, uint32_t L, SgDoc* out)
             }
             wave_sync();
 #ifdef EH_PROF
-            if (l == 0) { atomicAdd(&c.p->prof[2 * 94], (unsigned long long)N * rp_dtok); atomicAdd(&c.p->prof[2 * 94 + 1], 1ull); }   // tokens written by replay, replays
+            if (l == 0) { atomicAdd(&c.p->prof[2 * PROF_SG_REPLAY], (unsigned long long)N * rp_dtok); atomicAdd(&c.p->prof[2 * PROF_SG_REPLAY + 1], 1ull); }   // tokens written by replay, replays
 #endif
             ntok += N * rp_dtok; npc += N * rp_dpc; npar += N * rp_dpar;
             pos = rp_s0 + J * rp_P; ei = rp_e0 + J * rp_de;
@@ -611,7 +611,7 @@ __device__ __noinline__ int sgml_tokenize(Ctx&, cbptr H, uint32_t L, SgDoc* out)
             bbase = 0xFFFFFFFFu;
           }
 #ifdef EH_PROF
-          if (l == 0 && J <= 3) { atomicAdd(&c.p->prof[2 * 99 + 1], 1ull); atomicAdd(&c.p->prof[2 * 99], same ? 1ull : 0ull); }   // checked but not replayed; of them: look-ahead too long
+          if (l == 0 && J <= 3) { atomicAdd(&c.p->prof[2 * PROF_SG_NO_REPLAY + 1], 1ull); atomicAdd(&c.p->prof[2 * PROF_SG_NO_REPLAY], same ? 1ull : 0ull); }   // checked but not replayed; of them: look-ahead too long
 #endif
           rp_load(pos);                                                    // this stretch is done; is there another one ahead?
         } else if (rp_state != 0 && pos > rp_s0 + (uint32_t)rp_state * rp_P) {
@@ -619,7 +619,7 @@ __device__ __noinline__ int sgml_tokenize(Ctx&, cbptr H, uint32_t L, SgDoc* out)
           if (++rp_tries >= 8) {
             rp_load(rp_end);
 #ifdef EH_PROF
-            if (l == 0) atomicAdd(&c.p->prof[2 * 89 + 1], 1ull);        // gave up: never back in the state a period later
+            if (l == 0) atomicAdd(&c.p->prof[2 * PROF_SG_PERIOD_LOST + 1], 1ull);        // gave up: never back in the state a period later
 #endif
           }
         }
@@ -770,8 +770,8 @@ __device__ __noinline__ int sgml_tokenize(Ctx&, cbptr H, uint32_t L, SgDoc* out)
       bbase = 0xFFFFFFFFu;
       wave_sync();
 #ifdef EH_PROF
-      if (l == 0) { atomicAdd(&c.p->prof[2 * 85], (unsigned long long)(ttk / 2u)); atomicAdd(&c.p->prof[2 * 85 + 1], 1ull); }   // tags written by lane batches, batches
-      if (l == 0) { atomicAdd(&c.p->prof[2 * 68], (unsigned long long)__popcll(visited & ~accm)); atomicAdd(&c.p->prof[2 * 68 + 1], 1ull); }   // failed attempts committed by batches
+      if (l == 0) { atomicAdd(&c.p->prof[2 * PROF_SG_BATCH_TAGS], (unsigned long long)(ttk / 2u)); atomicAdd(&c.p->prof[2 * PROF_SG_BATCH_TAGS + 1], 1ull); }   // tags written by lane batches, batches
+      if (l == 0) { atomicAdd(&c.p->prof[2 * PROF_SG_BATCH_FAILED], (unsigned long long)__popcll(visited & ~accm)); atomicAdd(&c.p->prof[2 * PROF_SG_BATCH_FAILED + 1], 1ull); }   // failed attempts committed by batches
 #endif
       if (single && any_acc) { const int r = after_accept(); if (r) return r; }
     }
@@ -782,10 +782,10 @@ __device__ __noinline__ int sgml_tokenize(Ctx&, cbptr H, uint32_t L, SgDoc* out)
     uint32_t j = find(0, 1u << E_LT);
     lt = evget(j) >> 4; pos = lt + 1; ei = j + 1;
   }
-  SG_SUB(112);                                                             // set-up: tables, the first stretch search, the first '<'
+  SG_SUB(PROF_SG_SETUP);                                                             // set-up: tables, the first stretch search, the first '<'
   for (;;) {
     if (npc + 16 > cap_pc || ntok + 2 > cap_tok) { EH_SET_OVERFLOW(c, 601); return -3; }
-    SG_TZ(86);                                                             // eh_result_prof 86: text state + bookkeeping between attempts
+    SG_TZ(PROF_SG_TEXT);                                                             // eh_result_prof 86: text state + bookkeeping between attempts
     // ---- one tag attempt: '<' at lt, pos/ei just behind it
     skipws();
     const uint32_t tag0 = pos, ei0 = ei, tag_p0 = npc, par0 = npar;
@@ -934,7 +934,7 @@ __device__ __noinline__ int sgml_tokenize(Ctx&, cbptr H, uint32_t L, SgDoc* out)
               wave_sync();
               ab_penalty = 1;
 #ifdef EH_PROF
-              if (l == 0) { atomicAdd(&c.p->prof[2 * 120], (unsigned long long)cnt); atomicAdd(&c.p->prof[2 * 120 + 1], 1ull); }   // attributes written by attribute batches, batches
+              if (l == 0) { atomicAdd(&c.p->prof[2 * PROF_SG_ATTRS], (unsigned long long)cnt); atomicAdd(&c.p->prof[2 * PROF_SG_ATTRS + 1], 1ull); }   // attributes written by attribute batches, batches
 #endif
               continue;
             }
@@ -988,8 +988,8 @@ __device__ __noinline__ int sgml_tokenize(Ctx&, cbptr H, uint32_t L, SgDoc* out)
       }
     } while (false);
     if (c.status != CASE_OK) return -3;
-    if (ok) SG_TZ(88); else SG_TZ(87);                                     // 88: accepted tags, 87: failed attempts
-    SG_CNT(118, npar - par0);                                              // attributes the attempt walked
+    if (ok) SG_TZ(PROF_SG_TAG_OK); else SG_TZ(PROF_SG_TAG_FAILED);                                     // 88: accepted tags, 87: failed attempts
+    SG_CNT(PROF_SG_ATTRS_WALKED, npar - par0);                                              // attributes the attempt walked
     SG_SUB0();
     if (ok) {
       // the text before the tag (if any) and the tag itself
@@ -1005,7 +1005,7 @@ __device__ __noinline__ int sgml_tokenize(Ctx&, cbptr H, uint32_t L, SgDoc* out)
       pos = next; ei = nexte; seg_start = next; text_p0 = npc; text_len = 0;
       fail_run = 0;
       { const int r = after_accept(); if (r) return r; }
-      SG_SUB(113);
+      SG_SUB(PROF_SG_AFTER_ACCEPT);
     } else {
       if (first) { rc = other ? -2 : -1; break; }
       if (nchain > 0) {                                                    // remember where this attempt entered the attribute loop
@@ -1028,10 +1028,10 @@ __device__ __noinline__ int sgml_tokenize(Ctx&, cbptr H, uint32_t L, SgDoc* out)
     }
     SG_SUB0();
     { const int r = lane_batches(); if (r) return r; }
-    SG_SUB(114);
+    SG_SUB(PROF_SG_LANE_BATCHES);
     // ---- text state: ff/4 :166-174
     uint32_t j = find(ei, 1u << E_LT);
-    SG_SUB(115);
+    SG_SUB(PROF_SG_FIND_LT);
     if (j >= nev) {                                                        // {{text,Str},"",eof} :82-83,:94-95
       uint32_t n = L - seg_start;
       put(H + seg_start, n); text_len += n;
@@ -1178,7 +1178,7 @@ EH_DEV int sgml_finish(Ctx& c, cbptr H, uint32_t L, EH_G Piece* out, uint32_t no
   if (!dst) return 0;
   wave_gather(dst, out, nout);
   wave_sync();
-  EH_PT(c, 93);
+  EH_PT(c, PROF_SG_GATHER);
   if ((uint32_t)total == L && wave_equal(dst, H, L)) { tr_drop_before(c, meta0); return -1; }   // NewBinStr =:= H: {fun sgml_mutate/2, Ll, NewMeta, -1} :748-749 - NewMeta ALONE
   c.r_kind = R_NEW; c.r_ptr = dst; c.r_len = (uint32_t)total; c.r_changed = 1;
   return D + (int)(total / (AVG_BLOCK_SIZE * 10));
@@ -1265,7 +1265,7 @@ __device__ __noinline__ int muta_sgml(Ctx&) {
   if (!dh) return 0;
   EH_PT0;
   int rc = sgml_tokenize(c, H, L, dh);
-  EH_PT(c, 90);
+  EH_PT(c, PROF_SG_TOKENIZE);
   if (rc == -1) return -1;                                                 // catch incorrect_sgml :755-756
   if (rc == -2) { c.status = CASE_CRASHED; return 0; }
   if (rc != 0) return 0;
@@ -1277,7 +1277,7 @@ __device__ __noinline__ int muta_sgml(Ctx&) {
   sgml_pair(H, tok, ntok, stk);
   uint32_t N, NT;
   sgml_flags(tok, ntok, ef, &N, &NT);
-  EH_PT(c, 91);
+  EH_PT(c, PROF_SG_FLAGS);
   // output piece list: worst case every doc piece twice plus a few literals
   uint32_t cap_out = 2 * npc + 64;
   EH_G Piece* out = (EH_G Piece*)ws_alloc(c, (uint64_t)cap_out * sizeof(Piece));
@@ -1500,7 +1500,7 @@ __device__ __noinline__ int muta_sgml(Ctx&) {
     }
   }
   if (c.status != CASE_OK) return 0;
-  EH_PT(c, 92);
+  EH_PT(c, PROF_SG_MUTATE);
   return sgml_finish(c, H, L, out, nout, cap_out, D, meta0);
 }
 

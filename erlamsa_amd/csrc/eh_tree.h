@@ -66,8 +66,8 @@ static_assert(TL_ESC + 16 * TL_SP <= EH_FUSE_LDS_WORDS, "g_fuse_lds too small fo
 EH_DEV uint8_t* tl_bytes() { return reinterpret_cast<uint8_t*>(g_fuse_lds); }
 EH_DEV uint16_t* tl_stack() { return reinterpret_cast<uint16_t*>(g_fuse_lds + TL_STK); }
 #ifdef EH_PROF
-#define TR_PH(k) do { uint64_t now_ = __builtin_readcyclecounter(); if (EH_LANE == 0) { atomicAdd(&c.p->prof[2 * (70 + (k))], (unsigned long long)(now_ - tph)); atomicAdd(&c.p->prof[2 * (70 + (k)) + 1], 1ull); } tph = now_; } while (0)
-#define TR_ST(k, v) do { if (EH_LANE == 0) { atomicAdd(&c.p->prof[2 * (70 + (k))], (unsigned long long)(v)); atomicAdd(&c.p->prof[2 * (70 + (k)) + 1], 1ull); } } while (0)
+#define TR_PH(k) do { uint64_t now_ = __builtin_readcyclecounter(); if (EH_LANE == 0) { atomicAdd(&c.p->prof[2 * (PROF_TREE + (k))], (unsigned long long)(now_ - tph)); atomicAdd(&c.p->prof[2 * (PROF_TREE + (k)) + 1], 1ull); } tph = now_; } while (0)
+#define TR_ST(k, v) do { if (EH_LANE == 0) { atomicAdd(&c.p->prof[2 * (PROF_TREE + (k))], (unsigned long long)(v)); atomicAdd(&c.p->prof[2 * (PROF_TREE + (k)) + 1], 1ull); } } while (0)
 #else
 #define TR_PH(k) do { } while (0)
 #define TR_ST(k, v) do { } while (0)
@@ -383,7 +383,7 @@ __device__ __noinline__ int tree_parse(Ctx&, cbptr H, uint32_t L, EH_G TNode** o
   TR_PH(12);
 #ifdef EH_PROF
   // eh_result_prof slot 85: events, parses (above); slot 86: events decided by lane batches, quotes among the events
-  if (l == 0) { atomicAdd(&c.p->prof[2 * 86], (unsigned long long)nlane); atomicAdd(&c.p->prof[2 * 86 + 1], (unsigned long long)nquote); }
+  if (l == 0) { atomicAdd(&c.p->prof[2 * PROF_TREE_LANES], (unsigned long long)nlane); atomicAdd(&c.p->prof[2 * PROF_TREE_LANES + 1], (unsigned long long)nquote); }
 #endif
   (void)nlane; (void)nquote;
   // level end of every node: one past the close of the nearest ancestor that did close (L at top level).
